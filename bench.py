@@ -7,10 +7,14 @@ MI355X per rank.  One step = one ldpc_bp_decode_batch_dev launch over the
 65536 HBM-resident LLR frames (posterior + hard decision written back).
 Weak scaling: every rank decodes its own 65536-frame batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints one JSON line.  roofline: the decode kernel keeps every edge
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+line; --full adds the measurements that take runs of their own (`extras`: the other decoders,
+shapes and Monte-Carlo engines; `cpu_baseline`), which are null / empty otherwise.
+--dump-outputs DIR writes what the last timed step returned (post, hard, its; a fixed seeded
+sample of the frames) as DIR/<name>.npy.  roofline: the decode kernel keeps every edge
 message in LDS, so its binding unit is on-chip: LDS-array cycles (per CU,
 PMC SQ_LDS_IDX_ACTIVE) or VALU-busy cycles (per SIMD, PMC SQ_ACTIVE_INST_VALU)
 per codeword-iteration, both measured by counters in the committed profile of
@@ -41,6 +45,7 @@ ITERS = 50
 BATCH = 65536
 SIGMA = 0.85
 HBM_PEAK_GBPS = 8000.0
+DUMP_FRAMES, DUMP_SEED = 512, 0  # --dump-outputs: frames sampled from the batch, and the sampler's seed
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
@@ -54,7 +59,32 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the extras (other decoders, shapes, Monte-Carlo "
+                         "engines, the drop-in call surface) and the CPU baselines; --no-extras / "
+                         "--no-cpu-baseline drop one of the two again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (post, hard, its of a fixed seeded sample of "
+                         f"up to {DUMP_FRAMES} frames) as DIR/<name>.npy, float32")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the headline figure only
+        args.no_extras = args.no_cpu_baseline = True
+    return args
+
+
+def dump_outputs(path, post, hard, its):
+    """The timed path's outputs of its last step as path/<name>.npy (float32): posterior LLRs and
+    hard decisions of a fixed, seeded sample of frames (the same rows of both, ascending), and
+    the iteration count of every frame.  DUMP_FRAMES frames of n = 10,000 are 2 x 20.5 MB."""
+    import numpy as np
+    import torch
+    B = post.shape[0]
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(DUMP_FRAMES, B), replace=False))
+    idx = torch.from_numpy(rows).to(post.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "post.npy"), post.index_select(0, idx).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "hard.npy"), hard.index_select(0, idx).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "its.npy"), its.cpu().numpy().astype(np.float32))
 
 
 def host_cores():
@@ -415,6 +445,8 @@ def main():
         t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = float(t[0]), float(t[1])
+    if args.dump_outputs and rank == 0:  # before anything else writes post / hard / its
+        dump_outputs(args.dump_outputs, post, hard, its)
 
     # one collective over all ranks after the timed region: the frame errors of every rank's
     # own batch (RCCL over xGMI with the nccl backend) -- proves all N ranks joined and decoded

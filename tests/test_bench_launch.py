@@ -22,6 +22,18 @@ def test_single_gpu_default():
     assert a.gpus == 1 and not a.rehearse_on_one_gpu
 
 
+def test_plain_run_measures_the_headline_only():
+    """Without --full neither the extras nor the CPU baselines run; --full turns both on and
+    --no-extras / --no-cpu-baseline still drop one of them."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert a.no_extras and a.no_cpu_baseline
+    a = bench.parse(["--full"])
+    assert a.full and not a.no_extras and not a.no_cpu_baseline
+    a = bench.parse(["--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    assert a.no_cpu_baseline and not a.no_extras and a.dump_outputs == "out"
+
+
 def test_spawn_plan_rank_envs():
     mode, envs = bench.launch_plan(4, {"PATH": "/bin"}, 8)
     assert mode == "spawn" and len(envs) == 4
