@@ -69,6 +69,7 @@ def lib():
         "ldpc_debug_loc_layout": ([P, P, P, P, i, i, i, P, P, P, P], i),
         "ldpc_debug_loc_variant": ([P, P, P, P, i, i, i, P], i),
         "ldpc_debug_mc_plan": ([P, i64, i64, i64, i, i, P], i),
+        "ldpc_debug_bp_plan": ([P, P, P, P, i, i, i, P, i, P, P], i),
         "ldpc_debug_seq_stats": ([P, i], i),
         "ldpc_debug_peel_stats": ([P, i], i),
         "ldpc_debug_peel_cap": ([i], i),

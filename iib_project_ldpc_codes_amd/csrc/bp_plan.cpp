@@ -1,0 +1,183 @@
+// The launch plan of a soft-decoding call: which kernel runs, and its grid, LDS and scratch
+// layout.  Host-only and pure (no HIP call): bp_dispatch.hip launches from it, capi.cpp sizes
+// the scratch buffer and names the kernel from it, tests/test_bp_plan.py reads it through
+// ldpc_debug_bp_plan without a device.
+#include "ldpc_internal.hpp"
+
+// Compile-time switches of the selection (scripts/build_variants.sh); LDPC_LDS36_PREFETCH and
+// LDPC_GMEM_T, which the kernels' files read too, are in ldpc_internal.hpp.
+#ifndef LDPC_LDS36_MINSUM
+#define LDPC_LDS36_MINSUM 1  // (3,6) min-sum on bp_lds_kernel rather than bp_loc_kernel
+#endif
+#ifndef LDPC_LOC
+#define LDPC_LOC 1  // fixed-count decode on bp_loc_kernel when the graph has a local-edge layout
+#endif
+#ifndef LDPC_LOC_MSMC
+#define LDPC_LOC_MSMC 1  // (3,6) min-sum Monte-Carlo (with or without early stop) on bp_loc_kernel
+#endif
+#ifndef LDPC_LOC_HARD_ET
+#define LDPC_LOC_HARD_ET 1  // early-stop decodes without posteriors on bp_loc_kernel
+#endif
+#ifndef LDPC_LOC_ET_POST
+#define LDPC_LOC_ET_POST 1  // early-stop decodes with posteriors on bp_loc_kernel (slab, persistent grid)
+#endif
+#ifndef LDPC_LOC_PERSIST
+#define LDPC_LOC_PERSIST 1  // bp_loc_kernel early stop without posteriors: persistent grid on a counter (2: every launch; fixed count +0.4 %, noise)
+#endif
+#ifndef LDPC_LDS36_GRID
+#define LDPC_LDS36_GRID 256  // persistent grid of the LDS kernel under early stop (one per CU)
+#endif
+#ifndef LDPC_GMEM_GRID
+#define LDPC_GMEM_GRID 256  // one 1024-thread workgroup per CU, so the per-workgroup slabs stay cache-resident
+#endif
+#ifndef LDPC_GMEM_HYB
+#define LDPC_GMEM_HYB 1  // first ~38k message slots in LDS, the rest in the slab
+#endif
+
+namespace ldpc {
+namespace {
+
+constexpr size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+int loc_variant_of(const ldpc_graph &g) {
+    return loc_variant(g.loc_dlo, g.loc_dhi, g.loc_DVN, g.loc_dvn0, g.loc_dvn1, g.loc_abs0, g.loc_abs1, g.loc_T,
+                       g.loc_KP);
+}
+// messages | MC: per-iteration curve (16-byte padded) | min-sum MC: syndrome bits
+size_t loc_lds_bytes(const ldpc_graph &g, int iters, bool mc, bool syn) {
+    return pad16((size_t)std::max(g.loc_words + 64, g.n) * 4) + (mc ? pad16((size_t)(iters + 1) * 4) : 0) +
+           (syn ? (size_t)((g.m + 31) / 32) * 4 : 0);
+}
+// Early stop with posteriors on bp_loc_kernel: a VP x T float2 slab per workgroup
+size_t loc_ep_slab_bytes(const ldpc_graph &g) { return (size_t)(2 * g.loc_KP) * (size_t)g.loc_T * 2 * 4; }
+
+// bp_irr_kernel: LDS bytes (messages, syndrome bits, curve) and whether the slab is used
+size_t irr_lds_bytes(const ldpc_graph &g, int iters) {
+    const int nsyn = (g.m + 31) >> 5;
+    return pad16((size_t)g.irr_S * 4) + (size_t)((nsyn + 3) & ~3) * 4 + (size_t)(iters + 1) * 4;
+}
+bool irr_slab(const ldpc_graph &g) { return g.irr_S < g.irr_P; }
+
+size_t lds36_bytes(const ldpc_graph &g, int iters, bool et, bool mc) {
+    const size_t Ep = (size_t)lds_pair_span(g.m, 6) + kLdsDummy;
+    size_t s = Ep * 4;
+    if (et || mc) s = pad16(Ep * 5);
+    if (mc) s += (size_t)(iters + 1) * 4;
+    return s;
+}
+
+// bp_generic_kernel: every message (fp32) and sign byte of a codeword, and the posteriors
+size_t generic_msg_bytes(const ldpc_graph &g) { return pad16((size_t)g.E * 5 + (size_t)g.n * 4); }
+size_t generic_lds_bytes(const ldpc_graph &g, int iters, bool mc) {
+    return generic_msg_bytes(g) + (mc ? (size_t)(iters + 1) * 4 : 0);
+}
+
+BpPath choose_path(const ldpc_graph &g, int iters, bool et, bool mc, int algo, bool hard_only) {
+    if (!g.consistent) return BpPath::None;
+    // min-sum on (3,6) codes with one 1024-thread local-edge workgroup per CU: bp_lds_kernel
+    // is faster (its variable sums need no reordering); with the two-workgroup 512-thread
+    // shape the local-edge kernel wins (bench code: 2.00 vs 1.74 M cw/s); the local-edge
+    // kernel for everything else it covers
+    // (Monte-Carlo with or without early stop; early-stop decodes with hard decisions only;
+    // early-stop decodes that return posteriors when the message LDS can stage n posteriors +
+    // n decision bytes (ep_ok: the persistent grid with per-workgroup slabs); min-sum early
+    // stop: one check class)
+    const bool lds36_ms = LDPC_LDS36_MINSUM && algo == 1 && g.lane_var && g.dv == 3 && g.dc == 6 && g.loc_T != 512;
+    const bool one_cls = loc_variant_of(g) == kLocReg36;  // the one-class (3,6) instantiation
+    // early stop with posteriors stages n posteriors + n decision bytes in the message LDS
+    const bool ep_ok = LDPC_LOC_ET_POST && (size_t)std::max(g.loc_words + 64, g.n) * 4 >= (size_t)g.n * 5;
+    const bool mode_ok = mc ? (algo == 0 || (LDPC_LOC_MSMC && one_cls))
+                            : (!et || (LDPC_LOC_HARD_ET && (hard_only || ep_ok) && (algo == 0 || one_cls)));
+    const bool mset = et && algo == 1;
+    if (LDPC_LOC && mode_ok && iters > 0 && !lds36_ms && loc_variant_of(g) != kLocNone &&
+        loc_lds_bytes(g, iters, mc || mset, mset) <= kLdsMax - 2048)
+        return BpPath::Loc;
+    if (g.lane_var && g.dv == 3 && g.dc == 6 && lds36_bytes(g, iters, et, mc) <= kLdsMax - 2048)
+        return BpPath::Lds36;
+    if (g.irr_lane && irr_lds_bytes(g, iters) <= kLdsMax - 1024) return BpPath::Irr;
+    const int d = g.max_cdeg;
+    if (d > 32) return BpPath::None;
+    const bool lds = generic_lds_bytes(g, iters, mc) <= kLdsMax - 2048;
+    if (d <= 8) return lds ? BpPath::Generic8 : BpPath::GenericG8;
+    if (d <= 16) return lds ? BpPath::Generic16 : BpPath::GenericG16;
+    return lds ? BpPath::Generic32 : BpPath::GenericG32;
+}
+
+}  // namespace
+
+BpPlan bp_plan(const ldpc_graph &g, int B, int iters, int algo, bool et, bool mc, bool want_post, int cus) {
+    algo = algo ? 1 : 0;
+    BpPlan p;
+    p.path = choose_path(g, iters, et, mc, algo, !want_post);
+    p.grid = B;
+    size_t slab_per_wg = 0;
+    switch (p.path) {
+        case BpPath::Loc: {
+            p.name = "bp_loc_kernel";
+            p.threads = g.loc_T;
+            const bool mset = et && algo == 1;
+            p.lds = loc_lds_bytes(g, iters, mc || mset, mset);
+            // early stop with posteriors: persistent workgroups (two per CU, the most any
+            // bp_loc_kernel shape keeps resident), each with a slab; early stop without: the same
+            // grid on the counter alone
+            const bool ep = et && !mc && want_post;
+            p.persistent = ep || ((et || LDPC_LOC_PERSIST > 1) && LDPC_LOC_PERSIST);
+            if (p.persistent) p.grid = std::min(B, 2 * cus);
+            if (ep) slab_per_wg = loc_ep_slab_bytes(g);
+            break;
+        }
+        case BpPath::Lds36:
+            p.name = "bp_lds_kernel<3,6>";
+            p.threads = g.lane_T;
+            p.lds = lds36_bytes(g, iters, et, mc);
+            // with early stop, one workgroup per CU striding over the codewords beats a
+            // workgroup per codeword (+6 %: frames end at different iterations); fixed-count
+            // decodes: +1 % with the prefetch
+            if (et || (LDPC_LDS36_PREFETCH && !mc)) p.grid = std::min(B, LDPC_LDS36_GRID);
+            break;
+        case BpPath::Irr:
+            p.name = irr_slab(g) ? "bp_irr_kernel<lds+slab>" : "bp_irr_kernel<lds>";
+            p.threads = kIrrT;
+            p.lds = irr_lds_bytes(g, iters);
+            if (irr_slab(g)) {
+                p.grid = std::min(B, LDPC_GMEM_GRID);
+                slab_per_wg = (size_t)g.irr_P * 4;
+            }
+            break;
+        case BpPath::Generic8:
+        case BpPath::Generic16:
+        case BpPath::Generic32:
+            p.name = p.path == BpPath::Generic8    ? "bp_generic_kernel<8,lds>"
+                     : p.path == BpPath::Generic16 ? "bp_generic_kernel<16,lds>"
+                                                   : "bp_generic_kernel<32,lds>";
+            p.threads = 256;
+            p.lds = generic_lds_bytes(g, iters, mc);
+            break;
+        case BpPath::GenericG8:
+        case BpPath::GenericG16:
+        case BpPath::GenericG32: {
+            p.name = p.path == BpPath::GenericG8    ? "bp_generic_kernel<8,gmem>"
+                     : p.path == BpPath::GenericG16 ? "bp_generic_kernel<16,gmem>"
+                                                    : "bp_generic_kernel<32,gmem>";
+            p.threads = LDPC_GMEM_T;
+            p.grid = std::min(B, LDPC_GMEM_GRID);
+            p.lds = mc ? pad16((size_t)(iters + 1) * 4) : 0;  // the curve
+            // fill the rest of the CU's LDS with the first message slots
+            const size_t room = p.lds < kLdsMax - 4096 ? kLdsMax - 4096 - p.lds : 0;
+            p.lds_slots = LDPC_GMEM_HYB ? (int)std::min<size_t>((size_t)g.E, room / 4) : 0;
+            p.lds += (size_t)p.lds_slots * 4;
+            slab_per_wg = generic_msg_bytes(g);
+            break;
+        }
+        case BpPath::None: return p;
+    }
+    p.slab = slab_per_wg * (size_t)p.grid;
+    p.scratch = p.slab;
+    if (p.persistent) {
+        p.counter = (long)p.slab;
+        p.scratch += sizeof(uint32_t);
+    }
+    return p;
+}
+
+}  // namespace ldpc

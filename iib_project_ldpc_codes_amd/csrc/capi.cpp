@@ -378,38 +378,36 @@ bool build_irr_layout(const HostGraph &h, int &VPT, int &KC, int &DC, int &S, in
     return true;
 }
 
-// layouts = false: the BEC arrays only (the drop-in message_passing; no soft-decoder layouts)
-int device_graph(const HostGraph &h, ldpc_graph **out, bool layouts = true) {
-    int rc = require_device();
-    if (rc) return rc;
-    ldpc_graph *g = new ldpc_graph();
-    g->n = h.n; g->m = h.m; g->k = h.k;
-    g->E = (int)h.cvar.size();
-    g->dv = h.dv; g->dc = h.dc;
-    g->max_vdeg = h.max_vdeg; g->max_cdeg = h.max_cdeg;
-    g->consistent = h.consistent;
-    g->vchk_len = (int)h.vchk.size();
-    (void)hipGetDevice(&g->device);
-    hipError_t e = upload(&g->cvar, h.cvar);
-    if (e == hipSuccess) e = upload(&g->cptr, h.cptr);
-    if (e == hipSuccess) e = upload(&g->vptr, h.vptr);
-    if (e == hipSuccess) e = upload(&g->vchk, h.vchk);
-    if (e == hipSuccess && h.consistent) e = upload(&g->vslot, h.vslot);
+// The soft-decoder layouts of a graph, built on the host: the arrays device_graph uploads.
+struct HostLayouts {
+    std::vector<int32_t> lane_var, lane_slot, irr_lane, irr_cdeg;
+    LocLayout loc;
+};
+
+// Fills g's scalar fields and, with layouts, the kernels' layouts (L and the lane_* / irr_* /
+// loc_* scalars of g).  No device is touched; g's array pointers stay null.
+// loc_T: threads of the local-edge layout, 0 = the shipped choice (ldpc_debug_loc_variant asks
+// for a shape; the LDPC_LOC_T environment variable does the same for shape experiments).
+void host_layouts(const HostGraph &h, ldpc_graph &g, HostLayouts &L, bool layouts = true, int loc_T = 0) {
+    g.n = h.n; g.m = h.m; g.k = h.k;
+    g.E = (int)h.cvar.size();
+    g.dv = h.dv; g.dc = h.dc;
+    g.max_vdeg = h.max_vdeg; g.max_cdeg = h.max_cdeg;
+    g.consistent = h.consistent;
+    g.vchk_len = (int)h.vchk.size();
+    if (!layouts || !h.consistent) return;
     int T = 0, VPT = 0;
-    if (e == hipSuccess && layouts && h.consistent && h.dv == 3 && h.dc == 6 && lds_shape(h.n, T, VPT) &&
+    if (h.dv == 3 && h.dc == 6 && lds_shape(h.n, T, VPT) &&
         (size_t)(lds_pair_span(h.m, h.dc) + kLdsDummy) * 4 <= 150 * 1024) {
-        std::vector<int32_t> lv, ls;
-        build_lane_layout(h, T, VPT, lv, ls);
-        e = upload(&g->lane_var, lv);
-        if (e == hipSuccess) e = upload(&g->lane_slot, ls);
-        g->lane_T = T;
-        g->lane_VPT = VPT;
+        build_lane_layout(h, T, VPT, L.lane_var, L.lane_slot);
+        g.lane_T = T;
+        g.lane_VPT = VPT;
     }
     // LDPC_NO_LOC_LAYOUT=1 in the environment: no local-edge layout (tests run the
     // other kernels on the same graphs)
     const char *noloc = getenv("LDPC_NO_LOC_LAYOUT");
-    if (e == hipSuccess && layouts && h.consistent && LDPC_LOC_LAYOUT && !(noloc && noloc[0] == '1')) {
-        LocLayout L;
+    if (LDPC_LOC_LAYOUT && !(noloc && noloc[0] == '1')) {
+        LocLayout &K = L.loc;
         // threads: 256 for up to 1024 check pairs (4 per thread); (3,6) codes up to 2560 pairs:
         // 512 threads x 5 pairs, two workgroups per CU when both fit the LDS (the bench code:
         // +29 % over one 1024-thread workgroup, whose barriers idle the CU); 1024 for up to
@@ -417,39 +415,61 @@ int device_graph(const HostGraph &h, ldpc_graph **out, bool layouts = true) {
         // 10 per thread)
         const int P = h.m / 2;
         const bool r36 = h.dv == 3 && h.dc == 6;
-        L.T = P <= 1024 ? 256 : (r36 && P <= 2560 ? 512 : (P <= 3072 ? 1024 : 512));
-        if (const char *t = getenv("LDPC_LOC_T")) L.T = atoi(t);  // shape experiments
-        bool built = build_loc_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, L);
-        if (built && r36 && L.T == 512 && L.KP == 5 && (size_t)std::max(L.words + 64, h.n) * 4 > 80 * 1024) {
-            L = LocLayout();  // two workgroups would not fit one CU's LDS
-            L.T = 1024;
-            built = build_loc_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, L);
+        K.T = P <= 1024 ? 256 : (r36 && P <= 2560 ? 512 : (P <= 3072 ? 1024 : 512));
+        if (const char *t = getenv("LDPC_LOC_T")) K.T = atoi(t);  // shape experiments
+        if (loc_T) K.T = loc_T;
+        bool built = build_loc_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, K);
+        if (built && r36 && K.T == 512 && K.KP == 5 && (size_t)std::max(K.words + 64, h.n) * 4 > 80 * 1024) {
+            K = LocLayout();  // two workgroups would not fit one CU's LDS
+            K.T = 1024;
+            built = build_loc_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, K);
         }
         if (built) {
-            e = upload(&g->loc_var, L.var);
-            if (e == hipSuccess) e = upload(&g->loc_pos, L.pos);
-            if (e == hipSuccess) e = upload(&g->loc_info, L.info);
-            g->loc_T = L.T; g->loc_KP = L.KP; g->loc_DVN = L.DVN; g->loc_P = L.P;
-            g->loc_ncls = L.ncls; g->loc_words = L.words;
+            g.loc_T = K.T; g.loc_KP = K.KP; g.loc_DVN = K.DVN; g.loc_P = K.P;
+            g.loc_ncls = K.ncls; g.loc_words = K.words;
             int dlo = 99, dhi = 0;
-            const bool mix_ok = loc_degree_range(L, dlo, dhi);
-            g->loc_dlo = dlo; g->loc_dhi = dhi;
-            if (!mix_ok) g->loc_KP = 0;
-            for (int i = 0; i <= L.ncls; ++i) { g->loc_cls_q[i] = L.cls_q[i]; g->loc_cls_w[i] = L.cls_w[i]; }
-            for (int i = 0; i < L.ncls; ++i) g->loc_cls_d[i] = L.cls_d[i];
-            g->loc_dvn0 = L.DVN0; g->loc_dvn1 = L.DVN1;
-            g->loc_abs0 = L.ABS0; g->loc_abs1 = L.ABS1;
+            const bool mix_ok = loc_degree_range(K, dlo, dhi);
+            g.loc_dlo = dlo; g.loc_dhi = dhi;
+            if (!mix_ok) g.loc_KP = 0;
+            for (int i = 0; i <= K.ncls; ++i) { g.loc_cls_q[i] = K.cls_q[i]; g.loc_cls_w[i] = K.cls_w[i]; }
+            for (int i = 0; i < K.ncls; ++i) g.loc_cls_d[i] = K.cls_d[i];
+            g.loc_dvn0 = K.DVN0; g.loc_dvn1 = K.DVN1;
+            g.loc_abs0 = K.ABS0; g.loc_abs1 = K.ABS1;
+        } else {
+            K = LocLayout();
         }
     }
-    if (e == hipSuccess && layouts && h.consistent && !g->lane_var && LDPC_IRR) {
-        std::vector<int32_t> ln, cd;
+    if (L.lane_var.empty() && LDPC_IRR) {
         int VPT_ = 0, KC = 0, DC = 0, S = 0, P = 0;
-        if (build_irr_layout(h, VPT_, KC, DC, S, P, ln, cd)) {
-            e = upload(&g->irr_lane, ln);
-            if (e == hipSuccess) e = upload(&g->irr_cdeg, cd);
-            g->irr_VPT = VPT_; g->irr_KC = KC; g->irr_DC = DC; g->irr_S = S; g->irr_P = P;
+        if (build_irr_layout(h, VPT_, KC, DC, S, P, L.irr_lane, L.irr_cdeg)) {
+            g.irr_VPT = VPT_; g.irr_KC = KC; g.irr_DC = DC; g.irr_S = S; g.irr_P = P;
+        } else {
+            L.irr_lane.clear();
+            L.irr_cdeg.clear();
         }
     }
+}
+
+// layouts = false: the BEC arrays only (the drop-in message_passing; no soft-decoder layouts)
+int device_graph(const HostGraph &h, ldpc_graph **out, bool layouts = true) {
+    int rc = require_device();
+    if (rc) return rc;
+    ldpc_graph *g = new ldpc_graph();
+    HostLayouts L;
+    host_layouts(h, *g, L, layouts);
+    (void)hipGetDevice(&g->device);
+    hipError_t e = upload(&g->cvar, h.cvar);
+    if (e == hipSuccess) e = upload(&g->cptr, h.cptr);
+    if (e == hipSuccess) e = upload(&g->vptr, h.vptr);
+    if (e == hipSuccess) e = upload(&g->vchk, h.vchk);
+    if (e == hipSuccess && h.consistent) e = upload(&g->vslot, h.vslot);
+    if (e == hipSuccess) e = upload(&g->lane_var, L.lane_var);
+    if (e == hipSuccess) e = upload(&g->lane_slot, L.lane_slot);
+    if (e == hipSuccess) e = upload(&g->loc_var, L.loc.var);
+    if (e == hipSuccess) e = upload(&g->loc_pos, L.loc.pos);
+    if (e == hipSuccess) e = upload(&g->loc_info, L.loc.info);
+    if (e == hipSuccess) e = upload(&g->irr_lane, L.irr_lane);
+    if (e == hipSuccess) e = upload(&g->irr_cdeg, L.irr_cdeg);
     if (e != hipSuccess) {
         set_error(std::string("graph upload: ") + hipGetErrorString(e));
         ldpc_graph_destroy(g);
@@ -616,13 +636,42 @@ int ldpc_debug_loc_variant(const int32_t *check_ptr, const int32_t *check_var, c
     HostGraph h;
     int rc = host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h);
     if (rc) return rc;
-    LocLayout L;
-    L.T = T;
     *variant = kLocNone;
-    if (!h.consistent || !build_loc_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, L)) return LDPC_OK;
-    int dlo = 0, dhi = 0;
-    if (!loc_degree_range(L, dlo, dhi)) return LDPC_OK;
-    *variant = loc_variant(dlo, dhi, L.DVN, L.DVN0, L.DVN1, L.ABS0, L.ABS1, L.T, L.KP);
+    if (!h.consistent) return LDPC_OK;
+    ldpc_graph g;
+    HostLayouts L;
+    host_layouts(h, g, L, true, T);  // the shipped layout rules, at the asked-for thread count
+    *variant = loc_variant(g.loc_dlo, g.loc_dhi, g.loc_DVN, g.loc_dvn0, g.loc_dvn1, g.loc_abs0, g.loc_abs1, g.loc_T,
+                           g.loc_KP);
+    return LDPC_OK;
+}
+
+// The launch plans (bp_plan) of `count` soft-decoding calls on one graph, from the host layouts
+// alone.  calls[i] = {B, iters, algo, early_stop, mc, want_post}; out[i] = {path, threads, grid,
+// LDS bytes, lds_slots, persistent, slab bytes, counter offset (-1: none), scratch bytes};
+// names + 64 i: the kernel's display name.
+int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                       const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
+                       char *names) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
+    HostGraph h;
+    int rc = host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h);
+    if (rc) return rc;
+    ldpc_graph g;
+    HostLayouts L;
+    host_layouts(h, g, L);
+    // bp_plan reads only whether these are set: point them at the host arrays
+    g.lane_var = L.lane_var.empty() ? nullptr : L.lane_var.data();
+    g.irr_lane = L.irr_lane.empty() ? nullptr : L.irr_lane.data();
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 6 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        const BpPlan p = bp_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus);
+        int64_t *o = out + 9 * (size_t)i;
+        o[0] = (int64_t)p.path; o[1] = p.threads; o[2] = p.grid; o[3] = (int64_t)p.lds; o[4] = p.lds_slots;
+        o[5] = p.persistent; o[6] = (int64_t)p.slab; o[7] = p.counter; o[8] = (int64_t)p.scratch;
+        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+    }
     return LDPC_OK;
 }
 
@@ -781,7 +830,7 @@ int ldpc_bp_decode_batch_dev(const ldpc_graph *g, const float *d_llr, int B, int
     }
     if (B == 0) return LDPC_OK;
     float *scratch = nullptr;
-    const size_t sb = bp_scratch_bytes(*g, B, max_iters, algo, early_stop && d_post);
+    const size_t sb = bp_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, false, d_post != nullptr);
     if (sb) {
         std::lock_guard<std::mutex> lk(g_mu);
         Workspace &ws = workspace(stream);
@@ -826,7 +875,8 @@ int ldpc_bp_decode_batch(const int32_t *variable_to_check_list, const int32_t *c
         int32_t *di = static_cast<int32_t *>(ws.itsb.p);
         rc = 0;
         // scratch taken inside the _dev call (needs the lock released)
-        if (e == hipSuccess) e = ws.scratch.ensure(bp_scratch_bytes(*g, B, max_iters, algo, early_stop && post));
+        if (e == hipSuccess)
+            e = ws.scratch.ensure(bp_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, false, post != nullptr));
         if (B > 0) {
             // no posteriors asked for: early stop may take the hard-decision path (bp_loc_kernel)
             e = launch_bp_decode(*g, dl, B, max_iters, algo, alpha, early_stop, post ? dp : nullptr, dh, di, nullptr,
@@ -894,7 +944,7 @@ int ldpc_mc_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t se
     float *scratch = nullptr;
     size_t sbytes = 0;
     if (channel != LDPC_CH_BEC) {
-        const size_t sb = bp_scratch_bytes(*g, B, max_iters, algo, false);
+        const size_t sb = bp_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, true, false);
         if (sb) {
             LDPC_HIP(ws.scratch.ensure(sb));
             scratch = static_cast<float *>(ws.scratch.p);

@@ -1,4 +1,5 @@
-// Device helpers shared by the kernel translation units (ldpc_kernels.hip, sampler.hip).
+// Device helpers shared by the kernel translation units (bec.hip, bp_*.hip, mc_kernels.hip,
+// ml.hip, sampler.hip, peel.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -112,11 +113,13 @@ __device__ __forceinline__ float u01(uint32_t x) {
     return (float)(2u * (x >> 9) + 1u) * 5.9604644775390625e-8f;
 }
 
-struct ChanArgs {
+}  // namespace
+struct ChanArgs {  // (a member of the kernel argument structs the kernel files share: kernel_args.hpp)
     int kind;      // LDPC_CH_*
     float p, p2;   // see oracle_channel
     uint32_t k0, k1;
 };
+namespace {
 
 // Channel value of variable 4g + i of a codeword from its Philox block r (all-zero codeword).
 __device__ __forceinline__ float chan_soft_word(const ChanArgs &ch, const uint4 &r, int i) {

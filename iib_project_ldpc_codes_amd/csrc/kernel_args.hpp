@@ -1,0 +1,83 @@
+// Kernel argument structs and the launch entries the kernel files give each other.
+#pragma once
+#include "device_common.hpp"
+#include "ldpc_internal.hpp"
+
+namespace ldpc {
+
+struct BecArgs {
+    const int32_t *cvar, *cptr, *vptr, *vchk;
+    int n, m, dv, dc;  // dv, dc > 0: regular (pointers implicit)
+    uint8_t *words;
+    int32_t *errors, *its;
+    int max_iters;
+    // Monte-Carlo mode
+    ChanArgs ch;
+    uint64_t first_cw;
+    int32_t *trial;  // [B][max_iters+1]
+    // ensemble mode: codeword b decodes on its own graph (cvar / vchk + b*graph_stride)
+    int64_t graph_stride;
+};
+
+struct BpArgs {
+    const int32_t *cptr, *cvar, *vptr, *vslot;
+    int n, m, E, B;
+    const float *llr;
+    float *post;
+    uint8_t *hard;
+    int32_t *its;
+    int max_iters;
+    float alpha;
+    // Monte-Carlo mode
+    ChanArgs ch;
+    uint64_t first_cw;
+    int32_t *trial;  // [B][max_iters+1]
+    // generic kernel, messages in global scratch
+    float *scratch;
+    size_t scratch_bytes;  // (host) bytes at scratch: the launchers refuse a layout needing more
+    // LDS kernel lane layout (ldpc_graph::lane_var / lane_slot)
+    const int32_t *lane_var, *lane_slot;
+    int lds_slots;  // generic GMEM kernel: message slots [0, lds_slots) kept in LDS
+    // irregular kernel layout (ldpc_graph::irr_*)
+    const int32_t *irr_lane, *irr_cdeg;
+    int irr_KC, irr_S, irr_P;
+    // local-edge kernel layout (ldpc_graph::loc_*)
+    const int32_t *loc_var, *loc_pos, *loc_info;
+    int loc_P, loc_ncls, loc_words;
+    int loc_cls_q[5], loc_cls_d[4], loc_cls_w[5];
+    uint32_t *work;  // bp_loc_kernel early stop (persistent grid): next-codeword counter (zeroed per launch)
+};
+
+inline ChanArgs make_chan(int kind, float p, float p2, uint64_t seed) {
+    ChanArgs c;
+    c.kind = kind;
+    c.p = p;
+    c.p2 = p2;
+    c.k0 = (uint32_t)seed;
+    c.k1 = (uint32_t)(seed >> 32);
+    return c;
+}
+
+// One entry per soft kernel family (bp_lds.hip, bp_loc_spa.hip / bp_loc_ms.hip, bp_irr.hip,
+// bp_generic.hip): launches the instantiation for (algo, early stop, Monte-Carlo) with the
+// plan's grid, LDS and scratch layout.  bp_dispatch.hip has checked the scratch buffer.
+hipError_t launch_lds36(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, bool et, bool mc, hipStream_t s);
+hipError_t launch_loc_spa(const BpPlan &p, const ldpc_graph &g, BpArgs a, bool et, bool mc, hipStream_t s);
+hipError_t launch_loc_ms(const BpPlan &p, const ldpc_graph &g, BpArgs a, bool et, bool mc, hipStream_t s);
+hipError_t launch_irr(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, bool et, bool mc, hipStream_t s);
+hipError_t launch_generic(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, bool et, bool mc, hipStream_t s);
+// BEC Monte-Carlo on a fixed code (bec.hip): launch_mc_decode's erasure-channel half
+hipError_t launch_mc_bec(const ldpc_graph &g, float p, float p2, uint64_t seed, uint64_t first_cw, int B,
+                         int max_iters, int32_t *trial, int32_t *trial_its, hipStream_t stream);
+
+namespace {
+// Run-time (algo, early stop, Monte-Carlo) -> template arguments: f(int_c<ALGO>, bool_c<ET>, bool_c<MC>)
+template <typename F>
+hipError_t bp_modes(int algo, bool et, bool mc, F f) {
+    auto with_mc = [&](auto A, auto E) { return mc ? f(A, E, bool_c<true>()) : f(A, E, bool_c<false>()); };
+    auto with_et = [&](auto A) { return et ? with_mc(A, bool_c<true>()) : with_mc(A, bool_c<false>()); };
+    return algo == 0 ? with_et(int_c<0>()) : with_et(int_c<1>());
+}
+}  // namespace
+
+}  // namespace ldpc

@@ -1,5 +1,5 @@
 // Internal declarations shared by the C ABI (capi.cpp) and the kernels
-// (ldpc_kernels.hip).  Not part of the public ABI (see include/ldpc_mi355x.h).
+// (bec.hip, bp_*.hip, mc_kernels.hip, ml.hip, sampler.hip, peel.hip).  Not part of the public ABI (see include/ldpc_mi355x.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -109,7 +109,7 @@ constexpr size_t kIrrLdsMsgBytes = 148 * 1024;
 // n = 10^4, 3 % spare = 11 variables per thread packs with ~1.02 LDS cycles per
 // half-wave access, 2 % = 10 per thread with ~1.5 -- and is 5 % faster: the
 // variable phase is bound by per-lane work, not bank conflicts.)  Must match the
-// instantiations in ldpc_kernels.hip.
+// instantiations in bp_lds.hip.
 #ifndef LDPC_LDS_SPARE
 #define LDPC_LDS_SPARE 102  // lanes >= n * SPARE / 100 (fewer lanes beat fewer bank conflicts)
 #endif
@@ -127,6 +127,7 @@ inline bool lds_shape(int n, int &T, int &VPT) {
         if (1024L * v >= need) { VPT = v; return true; }
     return false;
 }
+constexpr size_t kLdsMax = 160 * 1024;  // LDS bytes of one CU (the launch plan and the BEC launchers budget against it)
 constexpr int kLdsDummy = 3 * 32 + 4;  // dummy message slots after the real ones (DV=3)
 
 // Message positions of the LDS-resident (3,6) kernel.  Checks are paired
@@ -145,7 +146,7 @@ namespace ldpc {
 
 void set_error(const std::string &msg);
 
-// Kernel launchers (ldpc_kernels.hip).  All asynchronous on `stream`.
+// Kernel launchers (bec.hip, bp_dispatch.hip, mc_kernels.hip, ml.hip).  All asynchronous on `stream`.
 // Return hipSuccess or the launch error.
 hipError_t launch_bec_decode(const ldpc_graph &g, uint8_t *d_words, int B, int max_iters,
                              int32_t *d_errors, int32_t *d_its, hipStream_t stream);
@@ -154,14 +155,40 @@ hipError_t launch_bp_decode(const ldpc_graph &g, const float *d_llr, int B, int 
                             float alpha, int early_stop, float *d_post, uint8_t *d_hard,
                             int32_t *d_its, hipStream_t stream, float *d_scratch, size_t scratch_bytes);
 
-// Bytes of global scratch launch_bp_decode / launch_mc_decode need for this graph/batch (0
-// when the messages fit in LDS); ep_slab: an early-stop decode that returns posteriors (the
-// local-edge kernel's per-workgroup slabs; no other mode uses them).
-// ep: an early-stop decode that returns posteriors (the slabs are sized only if it runs on bp_loc_kernel).
-// The launchers check the layout of the path that runs against scratch_bytes and refuse
-// (hipErrorInvalidValue) one that would not fit, so a sizing rule that drifts from the dispatch
-// fails loudly instead of writing past the buffer.
-size_t bp_scratch_bytes(const ldpc_graph &g, int B, int iters, int algo, bool ep);
+// Compile-time switches read on both sides of the launch (the rest: bp_plan.cpp, the kernels' files)
+#ifndef LDPC_LDS36_PREFETCH
+#define LDPC_LDS36_PREFETCH 1  // persistent LDS kernel (decode API) prefetching the next codeword's LLRs
+#endif
+#ifndef LDPC_GMEM_T
+#define LDPC_GMEM_T 1024  // threads of bp_generic_kernel<*,gmem>: one workgroup per CU
+#endif
+
+// The launch plan of one soft-decoding call (bp_plan.cpp): which kernel runs and everything the
+// launch needs, decided in one host-only function.  The launchers, the scratch sizing and the
+// kernel-name introspection all read it; nothing else re-derives these numbers.
+enum class BpPath { Loc, Lds36, Irr, Generic8, Generic16, Generic32, GenericG8, GenericG16, GenericG32, None };
+struct BpPlan {
+    BpPath path = BpPath::None;
+    const char *name = "none";  // display name (ldpc_bp_kernel_name)
+    int threads = 0, grid = 0;
+    size_t lds = 0;             // dynamic LDS bytes
+    int lds_slots = 0;          // bp_generic_kernel<*,gmem>: message slots [0, lds_slots) kept in LDS
+    bool persistent = false;    // bp_loc_kernel: the grid pulls codewords from a counter in scratch
+    size_t slab = 0;            // bytes of per-workgroup slabs at the start of scratch (0: none)
+    long counter = -1;          // byte offset of the work counter in scratch (-1: none)
+    size_t scratch = 0;         // total scratch bytes the launch needs
+};
+// Reads only scalar fields of g and the nullness of lane_var / irr_lane.  cus: compute units of
+// the device (device_cus()); mc: fused-channel Monte-Carlo; want_post: a decode that returns
+// posteriors.
+BpPlan bp_plan(const ldpc_graph &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post, int cus);
+// Compute units of the current device (256 when it cannot be queried), asked on every call:
+// devices launch from their own host threads, and the slabs and the grid must agree per device.
+int device_cus();
+
+// Bytes of global scratch launch_bp_decode / launch_mc_decode need for this call: bp_plan's.
+// The launchers refuse (hipErrorInvalidValue) a buffer smaller than that.
+size_t bp_scratch_bytes(const ldpc_graph &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post);
 
 hipError_t launch_channel(int channel, float p, float p2, uint64_t seed, uint64_t first_cw, int n,
                           int B, void *d_out, hipStream_t stream);

@@ -1,4 +1,4 @@
-// Local-edge layout of bp_loc_kernel (ldpc_kernels.hip), built on the host.
+// Local-edge layout of bp_loc_kernel (bp_loc.hpp), built on the host.
 // (cls_d[k] = dy, or dy | dx << 8 for a mixed class: see "checks sorted by degree".)
 //
 // Every variable gets ONE "local" edge: a perfect b-matching pairs each check with exactly

@@ -5,11 +5,7 @@
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
-C=iib_project_ldpc_codes_amd/csrc
-mkdir -p build_variants
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Iinclude -I$C "$@" \
-  -c $C/sampler.hip -o build_variants/sampler_$name.o
-/opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -fPIC $C/build/ldpc_kernels.o build_variants/sampler_$name.o $C/build/peel.o \
-  $C/build/capi.o $C/build/mc_run.o $C/build/loc_layout.o -Wl,--version-script=$C/exports.map -Wl,-Bsymbolic -ldl \
-  -o build_variants/$name.so
+rm -rf "build_variants/obj_$name"  # make tracks timestamps, not flags: always recompile the variant objects
+make -s -C iib_project_ldpc_codes_amd/csrc VARIANT_SRCS=sampler.hip VARIANT_OBJDIR="$PWD/build_variants/obj_$name" \
+  OUT="$PWD/build_variants/$name.so" EXTRA="$*"
 ls -la build_variants/$name.so

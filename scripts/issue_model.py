@@ -2,7 +2,8 @@
 
 usage: python scripts/issue_model.py <kernels.s> <pmc_summary.json> <out.json> [git-sha] [--kernel loc|lds36]
 
-<kernels.s>: `hipcc --cuda-device-only -S` of csrc/ldpc_kernels.hip with the Makefile's flags;
+<kernels.s>: `hipcc --cuda-device-only -S` of the kernel's file (csrc/bp_loc_spa.hip; lds36: csrc/bp_lds.hip) with the
+Makefile's flags;
 <pmc_summary.json>: scripts/pmc_summary.py output for one bench launch (B = 65,536, 50 iterations).
 
 The two on-chip units an LDS-resident decode kernel can saturate, per codeword-iteration:

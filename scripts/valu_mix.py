@@ -2,7 +2,7 @@
 
 usage: python scripts/valu_mix.py <kernels.s> <pmc_summary.json> <out.json> [git-sha]
 
-<kernels.s>: `hipcc --cuda-device-only -S` of csrc/ldpc_kernels.hip (same flags as the Makefile);
+<kernels.s>: `hipcc --cuda-device-only -S` of csrc/bp_lds.hip (same flags as the Makefile);
 <pmc_summary.json>: scripts/pmc_summary.py output of one bench launch (B = 65,536, 50 iterations)
 with SQ_INSTS_VALU and SQ_INSTS_VALU_TRANS_F32 (and the ADD/MUL/FMA_F32 class counters, which
 count a packed v_pk_* instruction once, in its class).

@@ -26,3 +26,66 @@ def check6_var24(m, seed=0):
     pairs = [(i, i) for i in range(m)] + [(i, (i + 1) % m) for i in range(m)]
     pairs += [(m + j, int(c)) for j in range(m) for c in rows[j]]
     return _csr_from_pairs(2 * m, m, np.full(m, 6, np.int32), pairs)
+
+
+def regular_simple(n, dv, dc, seed=0):
+    """A (dv, dc)-regular graph without repeated edges in the reference's list format, for
+    degrees where TannerGraph.random_regular's whole-graph redraw almost never succeeds: one
+    uniform socket permutation, then every slot that repeats a variable in its check swaps
+    variables with a random slot until none is left (not the configuration model's law)."""
+    from iib_project_ldpc_codes_amd.graph import TannerGraph
+    rng = np.random.default_rng(seed)
+    E, m = n * dv, n * dv // dc
+    assert m * dc == E
+    chk = np.arange(E) // dc
+    cvar = np.repeat(np.arange(n, dtype=np.int32), dv)[rng.permutation(E)]
+    for _ in range(1000):
+        key = chk.astype(np.int64) * n + cvar
+        order = np.argsort(key, kind="stable")
+        dup = order[1:][key[order][1:] == key[order][:-1]]
+        if not dup.size:
+            break
+        for s in dup:
+            t = rng.integers(E)
+            cvar[s], cvar[t] = cvar[t], cvar[s]
+    else:
+        raise RuntimeError("regular_simple: repeated edges left")
+    var = chk[np.lexsort((chk, cvar))].astype(np.int32)  # by variable, then ascending check
+    return TannerGraph(var, cvar, n, n - m, dv, dc)
+
+
+def csr_from_checks(cptr, cvar, n):
+    """CSR slot form (check_ptr, check_var, var_ptr, var_slot): each variable's slots ascending."""
+    cvar = np.ascontiguousarray(cvar, np.int32)
+    vslot = np.lexsort((np.arange(cvar.size), cvar)).astype(np.int32)
+    vptr = np.concatenate(([0], np.cumsum(np.bincount(cvar, minlength=n)))).astype(np.int32)
+    return np.ascontiguousarray(cptr, np.int32), cvar, vptr, vslot
+
+
+def bp_plans(csr, calls, cus=256, env=None):
+    """The soft decoders' launch plans (ldpc_debug_bp_plan, host only) of `calls` = (algo,
+    early_stop, mc, want_post, iters, B) tuples on one CSR graph; env: the environment of the
+    layout build (LDPC_NO_LOC_LAYOUT / LDPC_LOC_T), otherwise unset."""
+    import os
+    from iib_project_ldpc_codes_amd import _native
+    cptr, cvar, vptr, vslot = csr
+    args = np.ascontiguousarray([[B, iters, algo, es, mc, post] for algo, es, mc, post, iters, B in calls], np.int32)
+    out = np.zeros((len(calls), 9), np.int64)
+    names = np.zeros((len(calls), 64), np.uint8)
+    saved = {k: os.environ.pop(k, None) for k in ("LDPC_NO_LOC_LAYOUT", "LDPC_LOC_T")}
+    os.environ.update(env or {})
+    try:
+        rc = _native.lib().ldpc_debug_bp_plan(cptr.ctypes.data, cvar.ctypes.data, vptr.ctypes.data, vslot.ctypes.data,
+                                              vptr.size - 1, cptr.size - 1, len(calls), args.ctypes.data, cus,
+                                              out.ctypes.data, names.ctypes.data)
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+    assert rc == 0, _native.last_error()
+    keys = ("path", "threads", "grid", "lds", "lds_slots", "persistent", "slab", "counter", "scratch")
+    plans = [dict(zip(keys, (int(x) for x in row))) for row in out]
+    for p, nm in zip(plans, names):
+        p["name"] = nm.tobytes().split(b"\0")[0].decode()
+    return plans

@@ -1,5 +1,5 @@
 """Early-stop decodes that ask for hard decisions only (post == NULL) run on bp_loc_kernel
-(the stopping iteration's decisions kept in a bit per variable, csrc/ldpc_kernels.hip); the
+(the stopping iteration's decisions kept in a bit per variable, csrc/bp_loc.hpp); the
 posterior-returning early-stop decode runs on bp_loc_kernel's slab-and-replay instantiation
 where the message LDS can stage the posteriors (both the (3,6) codes and the ring code here),
 else on bp_lds_kernel / bp_irr_kernel.  Both must give what oracle_bp_decode (ldpc_oracle.c)

@@ -575,6 +575,28 @@ def test_mc_minsum_bsc_exact(torch, kind, early_stop):
     np.testing.assert_array_equal(got, want)
 
 
+def test_mc_generic_kernel_pushed_off_lds_by_max_iters(torch):
+    """(5,10) n = 5,500: the messages fit LDS beside a 500-iteration Monte-Carlo curve but not
+    beside a 600-iteration one, so the max_iters = 600 call runs bp_generic_kernel<16,gmem> on
+    per-workgroup slabs (once refused: the scratch buffer was sized by a rule that left this call
+    out).  Counters against the oracle; the curve against the LDS form of the same kernel."""
+    from tests.graph_util import bp_plans, csr_from_checks, regular_simple
+    g = regular_simple(5500, 5, 10, seed=1)
+    B = 32
+    pcsr = csr_from_checks(np.arange(g.m + 1) * 10, g.check_lookup, g.n)
+    names = [p["name"] for p in bp_plans(pcsr, [(1, 1, 1, 0, 600, B), (1, 1, 1, 0, 500, B)])]
+    assert names == ["bp_generic_kernel<16,gmem>", "bp_generic_kernel<16,lds>"]
+    got = _mc_counters(g, "bsc", 0.02, 8, B, 600, algo="minsum", alpha=0.75, early_stop=True)
+    csr = oracle.csr_from_lists(g.variable_lookup, g.check_lookup, g.n, g.m, 5, 10)
+    llr = oracle.channel(oracle.CH_BSC, 0.02, 8, 0, g.n, B)
+    _, h, its = oracle.bp_decode_batch(csr, llr, 600, 1, 0.75, True)
+    want = [B, int(h.any(axis=1).sum()), int(h.sum()), int(its.sum())]
+    print("counters 0-3: got", got[:4].tolist(), "oracle", want)
+    np.testing.assert_array_equal(got[:4], want)
+    lds = _mc_counters(g, "bsc", 0.02, 8, B, 500, algo="minsum", alpha=0.75, early_stop=True)
+    np.testing.assert_array_equal(got[4:4 + 501], lds[4:4 + 501])
+
+
 def test_parallel_simulator_fixed_code_device_engine(torch, tmp_path, monkeypatch):
     """run_simulation_fixed_ldpc (parallel_simulator.py:274-401 surface) on the device engine ==
     the oracle's sequential loop over the same Philox trials, including the 200-frame stop."""
