@@ -9,7 +9,7 @@ namespace {
 #endif
 // ---------------------------------------------------------------------------
 // 2b'. Irregular graphs (variable degree <= 4, check degree <= 8), one codeword
-// per 1024-thread workgroup, host-built layout (build_irr_layout, capi.cpp):
+// per 1024-thread workgroup, host-built layout (build_irr_layout, graph_host.cpp):
 //   check c = k*1024 + t is thread t's row-k check; its slot j sits at position
 //   (k*DC + j)*1024 + t, so a row's reads and writes are lane-contiguous (LDS
 //   conflict-free, coalesced in the slab).  Absent slots (degree < DC) hold the

@@ -1,7 +1,7 @@
 // The launch plan of a soft-decoding call: which kernel runs, and its grid, LDS and scratch
-// layout.  Host-only and pure (no HIP call): bp_dispatch.hip launches from it, capi.cpp sizes
-// the scratch buffer and names the kernel from it, tests/test_bp_plan.py reads it through
-// ldpc_debug_bp_plan without a device.
+// layout.  Host-only and pure (no HIP call): bp_dispatch.hip launches from it and answers the
+// entry points' scratch-size and kernel-name questions from it, tests/test_bp_plan.py reads it
+// through ldpc_debug_bp_plan without a device.
 #include "ldpc_internal.hpp"
 
 // Compile-time switches of the selection (scripts/build_variants.sh); LDPC_LDS36_PREFETCH and
@@ -39,26 +39,22 @@ namespace {
 
 constexpr size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
-int loc_variant_of(const ldpc_graph &g) {
-    return loc_variant(g.loc_dlo, g.loc_dhi, g.loc_DVN, g.loc_dvn0, g.loc_dvn1, g.loc_abs0, g.loc_abs1, g.loc_T,
-                       g.loc_KP);
-}
 // messages | MC: per-iteration curve (16-byte padded) | min-sum MC: syndrome bits
-size_t loc_lds_bytes(const ldpc_graph &g, int iters, bool mc, bool syn) {
+size_t loc_lds_bytes(const GraphShape &g, int iters, bool mc, bool syn) {
     return pad16((size_t)std::max(g.loc_words + 64, g.n) * 4) + (mc ? pad16((size_t)(iters + 1) * 4) : 0) +
            (syn ? (size_t)((g.m + 31) / 32) * 4 : 0);
 }
 // Early stop with posteriors on bp_loc_kernel: a VP x T float2 slab per workgroup
-size_t loc_ep_slab_bytes(const ldpc_graph &g) { return (size_t)(2 * g.loc_KP) * (size_t)g.loc_T * 2 * 4; }
+size_t loc_ep_slab_bytes(const GraphShape &g) { return (size_t)(2 * g.loc_KP) * (size_t)g.loc_T * 2 * 4; }
 
 // bp_irr_kernel: LDS bytes (messages, syndrome bits, curve) and whether the slab is used
-size_t irr_lds_bytes(const ldpc_graph &g, int iters) {
+size_t irr_lds_bytes(const GraphShape &g, int iters) {
     const int nsyn = (g.m + 31) >> 5;
     return pad16((size_t)g.irr_S * 4) + (size_t)((nsyn + 3) & ~3) * 4 + (size_t)(iters + 1) * 4;
 }
-bool irr_slab(const ldpc_graph &g) { return g.irr_S < g.irr_P; }
+bool irr_slab(const GraphShape &g) { return g.irr_S < g.irr_P; }
 
-size_t lds36_bytes(const ldpc_graph &g, int iters, bool et, bool mc) {
+size_t lds36_bytes(const GraphShape &g, int iters, bool et, bool mc) {
     const size_t Ep = (size_t)lds_pair_span(g.m, 6) + kLdsDummy;
     size_t s = Ep * 4;
     if (et || mc) s = pad16(Ep * 5);
@@ -67,12 +63,16 @@ size_t lds36_bytes(const ldpc_graph &g, int iters, bool et, bool mc) {
 }
 
 // bp_generic_kernel: every message (fp32) and sign byte of a codeword, and the posteriors
-size_t generic_msg_bytes(const ldpc_graph &g) { return pad16((size_t)g.E * 5 + (size_t)g.n * 4); }
-size_t generic_lds_bytes(const ldpc_graph &g, int iters, bool mc) {
+size_t generic_msg_bytes(const GraphShape &g) { return pad16((size_t)g.E * 5 + (size_t)g.n * 4); }
+size_t generic_lds_bytes(const GraphShape &g, int iters, bool mc) {
     return generic_msg_bytes(g) + (mc ? (size_t)(iters + 1) * 4 : 0);
 }
 
-BpPath choose_path(const ldpc_graph &g, int iters, bool et, bool mc, int algo, bool hard_only) {
+// The lane layout is present exactly when lane_T != 0 and the irregular one exactly when
+// irr_VPT != 0: host_layouts (graph_host.cpp) sets each only next to a builder that returned
+// non-empty arrays (build_lane_layout always fills T*VPT > 0 lanes; build_irr_layout's arrays are
+// cleared when it refuses), and a graph whose upload failed is never handed out.
+BpPath choose_path(const GraphShape &g, int iters, bool et, bool mc, int algo, bool hard_only) {
     if (!g.consistent) return BpPath::None;
     // min-sum on (3,6) codes with one 1024-thread local-edge workgroup per CU: bp_lds_kernel
     // is faster (its variable sums need no reordering); with the two-workgroup 512-thread
@@ -82,19 +82,19 @@ BpPath choose_path(const ldpc_graph &g, int iters, bool et, bool mc, int algo, b
     // early-stop decodes that return posteriors when the message LDS can stage n posteriors +
     // n decision bytes (ep_ok: the persistent grid with per-workgroup slabs); min-sum early
     // stop: one check class)
-    const bool lds36_ms = LDPC_LDS36_MINSUM && algo == 1 && g.lane_var && g.dv == 3 && g.dc == 6 && g.loc_T != 512;
-    const bool one_cls = loc_variant_of(g) == kLocReg36;  // the one-class (3,6) instantiation
+    const bool lds36_ms = LDPC_LDS36_MINSUM && algo == 1 && g.lane_T && g.dv == 3 && g.dc == 6 && g.loc_T != 512;
+    const bool one_cls = loc_variant(g) == kLocReg36;  // the one-class (3,6) instantiation
     // early stop with posteriors stages n posteriors + n decision bytes in the message LDS
     const bool ep_ok = LDPC_LOC_ET_POST && (size_t)std::max(g.loc_words + 64, g.n) * 4 >= (size_t)g.n * 5;
     const bool mode_ok = mc ? (algo == 0 || (LDPC_LOC_MSMC && one_cls))
                             : (!et || (LDPC_LOC_HARD_ET && (hard_only || ep_ok) && (algo == 0 || one_cls)));
     const bool mset = et && algo == 1;
-    if (LDPC_LOC && mode_ok && iters > 0 && !lds36_ms && loc_variant_of(g) != kLocNone &&
+    if (LDPC_LOC && mode_ok && iters > 0 && !lds36_ms && loc_variant(g) != kLocNone &&
         loc_lds_bytes(g, iters, mc || mset, mset) <= kLdsMax - 2048)
         return BpPath::Loc;
-    if (g.lane_var && g.dv == 3 && g.dc == 6 && lds36_bytes(g, iters, et, mc) <= kLdsMax - 2048)
+    if (g.lane_T && g.dv == 3 && g.dc == 6 && lds36_bytes(g, iters, et, mc) <= kLdsMax - 2048)
         return BpPath::Lds36;
-    if (g.irr_lane && irr_lds_bytes(g, iters) <= kLdsMax - 1024) return BpPath::Irr;
+    if (g.irr_VPT && irr_lds_bytes(g, iters) <= kLdsMax - 1024) return BpPath::Irr;
     const int d = g.max_cdeg;
     if (d > 32) return BpPath::None;
     const bool lds = generic_lds_bytes(g, iters, mc) <= kLdsMax - 2048;
@@ -105,7 +105,7 @@ BpPath choose_path(const ldpc_graph &g, int iters, bool et, bool mc, int algo, b
 
 }  // namespace
 
-BpPlan bp_plan(const ldpc_graph &g, int B, int iters, int algo, bool et, bool mc, bool want_post, int cus) {
+BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc, bool want_post, int cus) {
     algo = algo ? 1 : 0;
     BpPlan p;
     p.path = choose_path(g, iters, et, mc, algo, !want_post);

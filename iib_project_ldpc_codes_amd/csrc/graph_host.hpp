@@ -1,0 +1,43 @@
+// Graph preparation (graph_host.cpp): edge lists or CSR -> validated host graph -> the kernels'
+// layouts.  Host-only and pure: no HIP call, no environment variable (the C ABI reads the
+// environment into LayoutOptions, capi.cpp), so it links and runs without a device
+// (tests/host_layouts_main.cpp).
+#pragma once
+#include "errors.hpp"
+
+namespace ldpc {
+
+struct HostGraph {
+    int n = 0, m = 0, k = 0, dv = 0, dc = 0;
+    std::vector<int32_t> cvar, cptr, vptr, vchk, vslot;
+    bool consistent = false;
+    int max_vdeg = 0, max_cdeg = 0;
+};
+
+// Both validate their arguments and return LDPC_OK or LDPC_EINVAL (set_error says why).
+int host_graph_from_lists(const int32_t *v2c, const int32_t *c2v, int n, int k, int dv, int dc, HostGraph &h);
+int host_graph_from_csr(const int32_t *cptr, const int32_t *cvar, const int32_t *vptr, const int32_t *vslot, int n,
+                        int m, HostGraph &h);
+
+void build_lane_layout(const HostGraph &h, int T, int VPT, std::vector<int32_t> &lane_var,
+                       std::vector<int32_t> &lane_slot);
+bool build_irr_layout(const HostGraph &h, int &VPT, int &KC, int &DC, int &S, int &P, std::vector<int32_t> &lane,
+                      std::vector<int32_t> &cdeg);
+
+// The soft-decoder layouts of a graph, built on the host: the arrays device_graph uploads.
+struct HostLayouts {
+    std::vector<int32_t> lane_var, lane_slot, irr_lane, irr_cdeg;
+    LocLayout loc;
+};
+
+struct LayoutOptions {
+    bool loc_layout = true;  // build the local-edge layout (off: tests run the other kernels on the same graphs)
+    int loc_T = 0;           // threads of the local-edge layout, 0 = the shipped choice
+};
+
+// Fills g and, with layouts, the kernels' layouts (L and the lane_* / irr_* / loc_* scalars of g).
+// layouts = false: the BEC decoders' graph only (the drop-in message_passing).
+void host_layouts(const HostGraph &h, GraphShape &g, HostLayouts &L, bool layouts = true,
+                  const LayoutOptions &opt = LayoutOptions());
+
+}  // namespace ldpc

@@ -1,4 +1,4 @@
-// Internal declarations shared by the C ABI (capi.cpp) and the kernels
+// Internal declarations shared by the host files (capi.cpp, graph_host.cpp, graph_device.cpp, bp_plan.cpp) and the kernels
 // (bec.hip, bp_*.hip, mc_kernels.hip, ml.hip, sampler.hip, peel.hip).  Not part of the public ABI (see include/ldpc_mi355x.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,42 +8,48 @@
 #include <string>
 #include <vector>
 
-// Device-resident Tanner graph.  Slot e = position in the check-major edge
+// Shape of a prepared Tanner graph: every scalar of the graph and of its kernel layouts, filled
+// on the host (host_layouts, graph_host.cpp).  All that the launch plan (bp_plan.cpp) and the
+// launchers' sizing read; no device is involved.  Slot e = position in the check-major edge
 // list (the reference's check_lookup order, random_code_generator.c:34-36).
-struct ldpc_graph {
+struct GraphShape {
     int n = 0, m = 0, k = 0, E = 0;
     int dv = 0, dc = 0;          // > 0 when every variable / check has that degree
     int max_vdeg = 0, max_cdeg = 0;
     bool consistent = false;     // vslot defined: soft decoding allowed
+    int vchk_len = 0;            // length of vchk (E')
+    // Conflict-aware lane layout of the LDS-resident (3,6) kernel (build_lane_layout,
+    // graph_host.cpp): position p = t + i*T is thread t's i-th variable; every 32 consecutive
+    // positions form one half-wave LDS access.  lane_T == 0: none.
+    int lane_T = 0, lane_VPT = 0;
+    // Layout of the irregular kernel (bp_irr_kernel; build_irr_layout, graph_host.cpp):
+    // check c = k*1024 + t (thread t, row k < irr_KC), its slot j at position
+    // (k*irr_DC + j)*1024 + t; positions [0, irr_S) live in LDS, [irr_S, irr_P) in a
+    // per-workgroup global slab.  Lane p = i*1024 + t is thread t's i-th variable.  irr_VPT == 0: none.
+    int irr_VPT = 0, irr_KC = 0, irr_DC = 0, irr_S = 0, irr_P = 0;
+    // Local-edge layout of bp_loc_kernel (build_loc_layout, loc_layout.cpp); loc_KP == 0: none
+    int loc_T = 0, loc_KP = 0, loc_DVN = 0, loc_P = 0, loc_ncls = 0, loc_words = 0, loc_dlo = 0, loc_dhi = 0;
+    int loc_dvn0 = 0, loc_dvn1 = 0;       // non-local edges per variable, local slot 0 / 1 (max)
+    bool loc_abs0 = false, loc_abs1 = false;  // some variable of that slot has fewer
+    int loc_cls_q[5] = {0}, loc_cls_d[4] = {0}, loc_cls_w[5] = {0};
+};
+
+// Device-resident Tanner graph: the shape and the device arrays (listed once more, each with the
+// host vector it is filled from, in graph_device.cpp's for_graph_arrays).
+struct ldpc_graph : GraphShape {
     int device = 0;
-    // device arrays
     int32_t *cvar = nullptr;     // [E]   variable of each slot (check-major)
     int32_t *cptr = nullptr;     // [m+1] check c owns slots [cptr[c], cptr[c+1])
     int32_t *vptr = nullptr;     // [n+1] variable v owns edges [vptr[v], vptr[v+1])
     int32_t *vchk = nullptr;     // [E']  BEC: check id of each variable edge, -1 when
                                  //       that check holds v != 1 times (never assigns)
     int32_t *vslot = nullptr;    // [E]   soft: slot of each variable edge (consistent only)
-    int vchk_len = 0;
-    // Conflict-aware lane layout of the LDS-resident (3,6) kernel (see
-    // build_lane_layout in capi.cpp): position p = t + i*T is thread t's i-th
-    // variable; every 32 consecutive positions form one half-wave LDS access.
-    int lane_T = 0, lane_VPT = 0;
     int32_t *lane_var = nullptr;   // [T*VPT]    variable id, -1 = padding lane
     int32_t *lane_slot = nullptr;  // [T*VPT*dv] LDS position per edge (lds_pair_pos; padding
                                    //            lanes: dummy positions >= lds_pair_span)
-    // Layout of the irregular kernel (bp_irr_kernel; build_irr_layout in capi.cpp):
-    // check c = k*1024 + t (thread t, row k < irr_KC), its slot j at position
-    // (k*irr_DC + j)*1024 + t; positions [0, irr_S) live in LDS, [irr_S, irr_P) in a
-    // per-workgroup global slab.  Lane p = i*1024 + t is thread t's i-th variable.
-    int irr_VPT = 0, irr_KC = 0, irr_DC = 0, irr_S = 0, irr_P = 0;
     int32_t *irr_lane = nullptr;  // [3][1024*VPT]: variable id (-1 pad), positions j0|j1<<16, j2|j3<<16
                                   // (0xFFFF = no edge; lanes of one 64-lane row share a degree)
     int32_t *irr_cdeg = nullptr;  // [2][1024]: degrees of thread t's checks, 4 bits per row k
-    // Local-edge layout of bp_loc_kernel (build_loc_layout, loc_layout.cpp); loc_KP == 0: none
-    int loc_T = 0, loc_KP = 0, loc_DVN = 0, loc_P = 0, loc_ncls = 0, loc_words = 0, loc_dlo = 0, loc_dhi = 0;
-    int loc_dvn0 = 0, loc_dvn1 = 0;       // non-local edges per variable, local slot 0 / 1 (max)
-    bool loc_abs0 = false, loc_abs1 = false;  // some variable of that slot has fewer
-    int loc_cls_q[5] = {0}, loc_cls_d[4] = {0}, loc_cls_w[5] = {0};
     int32_t *loc_var = nullptr;   // [2*KP][2][T] variable id of var pair (thread, pair slot) half h, -1 pad
     int32_t *loc_pos = nullptr;   // [2*KP][DVN][T] non-local edge u's LDS words, h=0 | h=1 << 16
     int32_t *loc_info = nullptr;  // [2*KP][T] bit u + 4h: edge u present; bits 8+2h: local edge index jl;
@@ -79,6 +85,18 @@ inline bool loc_degree_range(const LocLayout &L, int &dlo, int &dhi) {
     return ok;
 }
 
+// The local-edge scalars of a graph's shape, from its built layout; loc_KP = 0 (no layout the
+// kernel can run) when the degree mix is outside loc_degree_range.
+inline void loc_shape(const LocLayout &K, GraphShape &g) {
+    g.loc_T = K.T; g.loc_KP = K.KP; g.loc_DVN = K.DVN; g.loc_P = K.P;
+    g.loc_ncls = K.ncls; g.loc_words = K.words;
+    if (!loc_degree_range(K, g.loc_dlo, g.loc_dhi)) g.loc_KP = 0;
+    for (int i = 0; i <= K.ncls; ++i) { g.loc_cls_q[i] = K.cls_q[i]; g.loc_cls_w[i] = K.cls_w[i]; }
+    for (int i = 0; i < K.ncls; ++i) g.loc_cls_d[i] = K.cls_d[i];
+    g.loc_dvn0 = K.DVN0; g.loc_dvn1 = K.DVN1;
+    g.loc_abs0 = K.ABS0; g.loc_abs1 = K.ABS1;
+}
+
 // The bp_loc_kernel instantiation family a local-edge layout runs on -- decided from the
 // WHOLE shape, never from the check degrees alone (a check-regular degree-6 graph with
 // variable degrees {2, 4} has loc_dlo == 6 but needs the RSU family's DVN = 3 rows):
@@ -97,6 +115,9 @@ inline int loc_variant(int dlo, int dhi, int DVN, int dvn0, int dvn1, bool abs0,
     if (reg36 && (common || (T == 512 && KP == 5))) return kLocReg36;
     if (rsu && (common || (T == 512 && (KP == 8 || KP == 10)))) return kLocRsu;
     return kLocNone;
+}
+inline int loc_variant(const GraphShape &g) {
+    return loc_variant(g.loc_dlo, g.loc_dhi, g.loc_DVN, g.loc_dvn0, g.loc_dvn1, g.loc_abs0, g.loc_abs1, g.loc_T, g.loc_KP);
 }
 
 // Irregular kernel (bp_irr_kernel): 1024 threads; LDS room for messages (bytes)
@@ -178,10 +199,9 @@ struct BpPlan {
     long counter = -1;          // byte offset of the work counter in scratch (-1: none)
     size_t scratch = 0;         // total scratch bytes the launch needs
 };
-// Reads only scalar fields of g and the nullness of lane_var / irr_lane.  cus: compute units of
-// the device (device_cus()); mc: fused-channel Monte-Carlo; want_post: a decode that returns
-// posteriors.
-BpPlan bp_plan(const ldpc_graph &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post, int cus);
+// cus: compute units of the device (device_cus()); mc: fused-channel Monte-Carlo; want_post: a
+// decode that returns posteriors.
+BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post, int cus);
 // Compute units of the current device (256 when it cannot be queried), asked on every call:
 // devices launch from their own host threads, and the slabs and the grid must agree per device.
 int device_cus();

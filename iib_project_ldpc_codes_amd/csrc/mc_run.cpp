@@ -37,8 +37,7 @@
 #include <thread>
 #include <vector>
 
-#include "ldpc_internal.hpp"
-#include "ldpc_mi355x.h"
+#include "errors.hpp"
 #include "mc_plan.hpp"
 
 using namespace ldpc;
@@ -58,7 +57,7 @@ struct Rccl {
 std::mutex g_run_mu;  // one multi-device run at a time (the comms and streams below)
 Rccl g_rccl;
 // Per device list: RCCL communicators and one stream per device, kept for the
-// process lifetime (the per-(device, stream) workspaces of capi.cpp are reused).
+// process lifetime (the per-(device, stream) workspaces of workspace.hpp are reused).
 struct Ctx {
     std::vector<ncclComm_t> comms;
     std::vector<hipStream_t> streams;
@@ -307,10 +306,8 @@ struct SeqBackend {
     int64_t trials() const { return G[0]; }
     int count(int64_t first, int B, int64_t quota, int64_t &t, int64_t &f) const {
         t = f = 0;
-        if (B > 0 && first + B > avail) {
-            set_error("ldpc_debug_mc_plan: the plan reads past the synthetic trial sequence");
-            return LDPC_EINVAL;
-        }
+        LDPC_REQUIRE(B <= 0 || first + B <= avail,
+                     "ldpc_debug_mc_plan: the plan reads past the synthetic trial sequence");
         for (int j = 0; j < B; ++j) {
             ++t;
             f += fe[first + j] != 0;
@@ -347,29 +344,20 @@ struct SeqBackend {
 };
 
 int check_common(int channel, int max_iters, int batch, const int *devices, int ndev, int64_t *counters) {
-    if (!counters || !devices || ndev <= 0 || max_iters < 0 || batch <= 0) {
-        set_error("ldpc_mc_run: need counters, devices[ndev > 0], max_iters >= 0, batch > 0");
-        return LDPC_EINVAL;
-    }
-    if (channel != LDPC_CH_BEC && channel != LDPC_CH_BSC && channel != LDPC_CH_AWGN) {
-        set_error("ldpc_mc_run: unknown channel");
-        return LDPC_EINVAL;
-    }
+    LDPC_REQUIRE(counters && devices && ndev > 0 && max_iters >= 0 && batch > 0,
+                 "ldpc_mc_run: need counters, devices[ndev > 0], max_iters >= 0, batch > 0");
+    LDPC_REQUIRE(channel == LDPC_CH_BEC || channel == LDPC_CH_BSC || channel == LDPC_CH_AWGN,
+                 "ldpc_mc_run: unknown channel");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
         set_error("libldpc_mi355x: no HIP device visible (this library has no CPU path; run on an MI355X)");
         return LDPC_ENODEV;
     }
     for (int i = 0; i < ndev; ++i) {
-        if (devices[i] < 0 || devices[i] >= count) {
-            set_error("ldpc_mc_run: device ordinal out of range");
-            return LDPC_EINVAL;
-        }
+        LDPC_REQUIRE(devices[i] >= 0 && devices[i] < count, "ldpc_mc_run: device ordinal out of range");
         for (int j = 0; j < i; ++j)
-            if (devices[j] == devices[i]) {
-                set_error("ldpc_mc_run: a device is listed twice (RCCL needs one rank per device)");
-                return LDPC_EINVAL;
-            }
+            LDPC_REQUIRE(devices[j] != devices[i],
+                         "ldpc_mc_run: a device is listed twice (RCCL needs one rank per device)");
     }
     return LDPC_OK;
 }
@@ -382,18 +370,13 @@ int ldpc_mc_run(const int32_t *variable_to_check_list, const int32_t *check_to_v
                 int dc, int channel, float param, int algo, float alpha, int early_stop, uint64_t seed,
                 int max_iters, int expurgation, int64_t num_tests, int64_t stop_frame_errors, int batch,
                 double time_limit_s, const int *devices, int ndev, int64_t *counters, int64_t *rounds) {
-    int rc = check_common(channel, max_iters, batch, devices, ndev, counters);
-    if (rc) return rc;
+    LDPC_TRY(check_common(channel, max_iters, batch, devices, ndev, counters));
     Run r;
     r.ensemble = (variable_to_check_list == nullptr && check_to_variable_list == nullptr);
-    if (r.ensemble && channel != LDPC_CH_BEC) {
-        set_error("ldpc_mc_run: ensemble mode (NULL edge lists) is defined for the BEC");
-        return LDPC_EINVAL;
-    }
-    if (!r.ensemble && (!variable_to_check_list || !check_to_variable_list)) {
-        set_error("ldpc_mc_run: give both edge lists (fixed code) or neither (ensemble)");
-        return LDPC_EINVAL;
-    }
+    LDPC_REQUIRE(!r.ensemble || channel == LDPC_CH_BEC,
+                 "ldpc_mc_run: ensemble mode (NULL edge lists) is defined for the BEC");
+    LDPC_REQUIRE(r.ensemble || (variable_to_check_list && check_to_variable_list),
+                 "ldpc_mc_run: give both edge lists (fixed code) or neither (ensemble)");
     r.v2c = variable_to_check_list;
     r.c2v = check_to_variable_list;
     r.n = n; r.k = k; r.dv = dv; r.dc = dc;
@@ -408,12 +391,8 @@ int ldpc_mc_run_csr(const int32_t *check_ptr, const int32_t *check_var, const in
                     int early_stop, uint64_t seed, int max_iters, int expurgation, int64_t num_tests,
                     int64_t stop_frame_errors, int batch, double time_limit_s, const int *devices, int ndev,
                     int64_t *counters, int64_t *rounds) {
-    int rc = check_common(channel, max_iters, batch, devices, ndev, counters);
-    if (rc) return rc;
-    if (!check_ptr || !check_var || !var_ptr || !var_slot) {
-        set_error("ldpc_mc_run_csr: null CSR array");
-        return LDPC_EINVAL;
-    }
+    LDPC_TRY(check_common(channel, max_iters, batch, devices, ndev, counters));
+    LDPC_REQUIRE(check_ptr && check_var && var_ptr && var_slot, "ldpc_mc_run_csr: null CSR array");
     Run r;
     r.cptr = check_ptr; r.cvar = check_var; r.vptr = var_ptr; r.vslot = var_slot;
     r.n = n; r.m = m;
@@ -425,10 +404,8 @@ int ldpc_mc_run_csr(const int32_t *check_ptr, const int32_t *check_var, const in
 
 int ldpc_debug_mc_plan(const uint8_t *frame_error, int64_t num_trials, int64_t num_tests, int64_t stop_frame_errors,
                        int batch, int ndev, int64_t *out) {
-    if (!out || (num_trials > 0 && !frame_error) || num_trials < 0 || batch <= 0 || ndev <= 0) {
-        set_error("ldpc_debug_mc_plan: need out[3], the trial sequence, batch > 0, ndev > 0");
-        return LDPC_EINVAL;
-    }
+    LDPC_REQUIRE(out && (num_trials <= 0 || frame_error) && num_trials >= 0 && batch > 0 && ndev > 0,
+                 "ldpc_debug_mc_plan: need out[3], the trial sequence, batch > 0, ndev > 0");
     McPlan P;
     P.num_tests = num_tests;
     P.stop = stop_frame_errors;
