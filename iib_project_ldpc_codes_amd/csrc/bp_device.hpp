@@ -98,13 +98,54 @@ __device__ __forceinline__ float2 pk_fma(float2 a, float2 b, float2 c) {
 // Check-node update over D messages in registers; entries i >= d are padding (+inf
 // for min-sum; skipped by sum-product).  Min-sum is bit-exact with oracle
 // check_update_ms; sum-product agrees with the oracle's exact rule to the stated
-// tolerance.
+// tolerance (tests/test_gpu_fallback.py for D > 6).
 template <int ALGO, int D, bool WIRE = false>
 __device__ __forceinline__ void check_update(float (&x)[D], float alpha, int d = D) {
-    if (ALGO == 0) {
+    if constexpr (ALGO == 0 && D > 6) {
+        // The same elementary-symmetric form, rescaled per input: e_k of the form below reaches
+        // 2^(23 k), so six saturated inputs overflow fp32 (degree >= 7: inf * 0 = NaN).  The
+        // (E, O) recurrence is homogeneous in each input's pair (1, R), so an input with R > 1
+        // enters as (1 / R, 1): with r = 2^-|x| <= 1,
+        //   R > 1:   (E, O) <- (r E + O, r O + E)        otherwise:   (E, O) <- (E + r O, O + r E).
+        // E + O = prod (1 + r_i) <= 2^31 and min(E, O) >= sum r_i >= 2^-23 at 32 inputs, all terms
+        // positive; the output ratio num / den is unchanged (oracle algo 3 restates it).
+        float r[D];
+        bool big[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            if constexpr (WIRE) {
+                big[i] = x[i] > 1.0f;
+                r[i] = big[i] ? __builtin_amdgcn_rcpf(x[i]) : x[i];
+            } else {
+                big[i] = x[i] > 0.0f;
+                r[i] = __builtin_amdgcn_exp2f(-fminf(fabsf(x[i]), 23.0f));
+            }
+        }
+        auto grow = [](float2 s, float ri, bool bi) {  // (E, O) of the set plus one input
+            const float2 t = make_float2(s.y, s.x);
+            return pk_fma(make_float2(ri, ri), bi ? s : t, bi ? t : s);
+        };
+        float2 pre[D];  // scaled (E, O) of inputs {0 .. i-1}
+        pre[0] = make_float2(1.0f, 0.0f);
+#pragma unroll
+        for (int i = 1; i < D; ++i) pre[i] = i - 1 < d ? grow(pre[i - 1], r[i - 1], big[i - 1]) : pre[i - 1];
+        const bool odd = (d - 1) & 1;
+        float2 suf = make_float2(1.0f, 0.0f);  // scaled (E, O) of inputs {j+1 .. d-1}
+#pragma unroll
+        for (int j = D - 1; j >= 0; --j) {
+            if (j < d) {
+                const float E = fmaf(pre[j].x, suf.x, pre[j].y * suf.y), O = fmaf(pre[j].x, suf.y, pre[j].y * suf.x);
+                const float num = odd ? O : E, den = odd ? E : O;
+                const float2 ns = grow(suf, r[j], big[j]);
+                x[j] = __builtin_amdgcn_logf(num * __builtin_amdgcn_rcpf(den));
+                suf = ns;
+            }
+        }
+    } else if (ALGO == 0) {
         // elementary-symmetric form (check_update_spa_pair_rwire) on the d inputs' ratios
         // R = 2^x (WIRE: the ratios themselves), outputs log2 of the exclusive ratio; (E, O)
         // sums in float2 so both chains are packed ops.  Entries i >= d are skipped.
+        // D <= 6 only: five inputs' e_k stay below 2^118.
         float R[D];
 #pragma unroll
         for (int i = 0; i < D; ++i)

@@ -257,7 +257,9 @@ hipError_t launch_irr_modes(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipS
     a.irr_P = g.irr_P;
 #define IRR_CASE(DC, VPT) \
     if (g.irr_DC == DC && g.irr_VPT == VPT) return launch_irr_shape<DC, VPT, ALGO, ET, MC>(p, a, s);
-    IRR_CASE(6, 5) IRR_CASE(6, 10) IRR_CASE(6, 20) IRR_CASE(8, 5) IRR_CASE(8, 10) IRR_CASE(8, 20)
+    // every VPT build_irr_layout hands out (1 and 2: graphs of up to 1024 / 2048 variable lanes)
+    IRR_CASE(6, 1) IRR_CASE(6, 2) IRR_CASE(6, 5) IRR_CASE(6, 10) IRR_CASE(6, 20)
+    IRR_CASE(8, 1) IRR_CASE(8, 2) IRR_CASE(8, 5) IRR_CASE(8, 10) IRR_CASE(8, 20)
 #undef IRR_CASE
     return hipErrorInvalidValue;
 }

@@ -109,7 +109,8 @@ def csr_from_lists(v2c, c2v, n, m, dv, dc):
 
 
 def bp_decode_batch(csr, llr, max_iters, algo=0, alpha=1.0, early_stop=False):
-    """Soft flooding decoder (algo 0 = sum-product, 1 = normalized min-sum)."""
+    """Soft flooding decoder (algo 0 = sum-product, 1 = normalized min-sum; 2 / 3 = the kernels'
+    fp32 sum-product forms for check degree <= 6 / the rescaled one of degrees 7-32)."""
     cptr, cvar, vptr, vslot = [np.ascontiguousarray(a, dtype=np.int32) for a in csr]
     n = vptr.shape[0] - 1
     m = cptr.shape[0] - 1

@@ -54,6 +54,85 @@ def regular_simple(n, dv, dc, seed=0):
     return TannerGraph(var, cvar, n, n - m, dv, dc)
 
 
+def mixed_checks(degrees, n, seed=0):
+    """A graph whose check c has degree degrees[c] (any multiset, every degree >= 2) on n
+    variables, as (check_ptr, check_var): the sum(degrees) sockets are dealt to the variables as
+    evenly as they divide (variable degrees floor / ceil of E / n) by one uniform socket
+    permutation, then every slot that repeats a variable in its check swaps variables with a
+    random slot until none is left, as regular_simple does."""
+    rng = np.random.default_rng(seed)
+    degrees = np.asarray(degrees, np.int64)
+    assert degrees.min() >= 2 and degrees.max() <= n
+    cptr = np.concatenate(([0], np.cumsum(degrees)))
+    E = int(cptr[-1])
+    assert E >= n
+    chk = np.repeat(np.arange(degrees.size), degrees)
+    cvar = (np.arange(E, dtype=np.int32) % n)[rng.permutation(E)]
+    for _ in range(1000):
+        key = chk.astype(np.int64) * n + cvar
+        order = np.argsort(key, kind="stable")
+        dup = order[1:][key[order][1:] == key[order][:-1]]
+        if not dup.size:
+            break
+        for s in dup:
+            t = rng.integers(E)
+            cvar[s], cvar[t] = cvar[t], cvar[s]
+    else:
+        raise RuntimeError("mixed_checks: repeated edges left")
+    return cptr.astype(np.int32), cvar
+
+
+def extreme_llrs(n, B, seed):
+    """BI-AWGN LLRs with the values at the edges of fp32 that a kernel can mishandle mixed in:
+    0 and -0, +-1e-30, +-1e4, +-1e30 (beyond the kernels' staging clamp)."""
+    from oracle import oracle
+    rs = np.random.RandomState(seed)
+    llr = oracle.channel(oracle.CH_AWGN, 0.80, seed, 0, n, B)
+    sign = np.where(rs.rand(B, n) < 0.5, -1.0, 1.0).astype(np.float32)
+    u = rs.rand(B, n)
+    llr = np.where(u < 0.08, 0.0, llr)
+    llr = np.where((u >= 0.08) & (u < 0.10), sign * 1e-30, llr)
+    llr = np.where((u >= 0.10) & (u < 0.14), sign * 1e4, llr)
+    llr = np.where((u >= 0.14) & (u < 0.16), sign * 1e30, llr)
+    llr[:, 0] = -0.0
+    return np.ascontiguousarray(llr, np.float32)
+
+
+# Graphs off the headline path: name -> the kernel a plain 20-iteration decode of 24 frames runs
+# (tests/test_bp_plan.py and tests/test_gpu_fallback.py hold the plan to these names).
+# r<dv><dc>_<n> is regular_simple(n, dv, dc, seed=1); mixA / mixB are mixed_checks graphs.
+FALLBACK_KERNELS = {
+    "r48_256": "bp_irr_kernel<lds>",            # DC = 8, every message in LDS
+    "r48_9216": "bp_irr_kernel<lds+slab>",      # DC = 8, rows beyond LDS in the slab
+    "r58_320": "bp_generic_kernel<8,lds>",      # variable degree 5 > kGenDV: the looped variable branch
+    "r58_8800": "bp_generic_kernel<8,gmem>",    # E = 44,000 > 39,936 LDS slots: messages in the slab
+    "r510_640": "bp_generic_kernel<16,lds>",
+    "r510_9000": "bp_generic_kernel<16,gmem>",  # E = 45,000
+    "r324_1024": "bp_generic_kernel<32,lds>",
+    "r432_2048": "bp_generic_kernel<32,lds>",
+    "r432_12288": "bp_generic_kernel<32,gmem>",  # E = 49,152
+    "mixA": "bp_irr_kernel<lds>",               # check degrees {2,3,5,7,8}, variable degrees 3 / 4
+    "mixB": "bp_generic_kernel<32,lds>",        # check degrees {2,9,16,17,31,32}: even / odd d, padding at every width
+}
+_REGULAR = {"r48": (4, 8), "r58": (5, 8), "r510": (5, 10), "r324": (3, 24), "r432": (4, 32)}
+_MIXED = {"mixA": (((2, 150), (3, 211), (5, 190), (7, 230), (8, 222)), 1400),
+          "mixB": (((2, 40), (9, 30), (16, 25), (17, 25), (31, 12), (32, 12)), 700)}
+
+
+def fallback_csr(name):
+    """CSR slot form of a FALLBACK_KERNELS graph."""
+    if name in _MIXED:
+        classes, n = _MIXED[name]
+        deg = np.concatenate([np.full(c, d) for d, c in classes])
+        deg = deg[np.random.default_rng(5).permutation(deg.size)]  # degree classes interleaved
+        cptr, cvar = mixed_checks(deg, n, seed=1)
+        return csr_from_checks(cptr, cvar, n)
+    kind, n = name.split("_")
+    dv, dc = _REGULAR[kind]
+    g = regular_simple(int(n), dv, dc, seed=1)
+    return csr_from_checks(np.arange(g.m + 1) * dc, g.check_lookup, g.n)
+
+
 def csr_from_checks(cptr, cvar, n):
     """CSR slot form (check_ptr, check_var, var_ptr, var_slot): each variable's slots ascending."""
     cvar = np.ascontiguousarray(cvar, np.int32)

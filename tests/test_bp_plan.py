@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from iib_project_ldpc_codes_amd import ensembles
-from tests.graph_util import bp_plans, csr_from_checks, regular_simple
+from tests.graph_util import FALLBACK_KERNELS, bp_plans, csr_from_checks, fallback_csr, regular_simple
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "bp_plan_parent.json")
 
@@ -27,6 +27,7 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "bp_plan_parent.json"
 CALLS = list(itertools.product((0, 1), (0, 1), (0, 1), (0, 1), (0, 1, 50, 600), (1, 300, 70000)))
 GRAPHS = ["r36_1000", "r36_4000", "r36_10000", "r36_64800", "rsu_2000", "rsu_20000", "r48_1000", "r510_1000",
           "r510_5500", "r510_8000", "deg33", "r36_10000_noloc"]
+FALLBACK = ["fb_" + k for k in FALLBACK_KERNELS]  # the graphs of tests/test_gpu_fallback.py (not in the parent table)
 KIB = 1024
 
 
@@ -34,6 +35,8 @@ KIB = 1024
 def graph_csr(name):
     """((check_ptr, check_var, var_ptr, var_slot), environment of the layout build)"""
     env = {"LDPC_NO_LOC_LAYOUT": "1"} if name.endswith("_noloc") else {}
+    if name.startswith("fb_"):
+        return fallback_csr(name[3:]), env
     kind, n = name.split("_")[0], name.split("_")[1] if "_" in name else None
     if kind == "rsu":
         g = ensembles.sample_irregular(ensembles.RSU_DL4, int(n), seed=1, deg2="zigzag")
@@ -86,7 +89,7 @@ def test_generic_mc_call_pushed_off_lds_gets_its_slabs():
     assert hit == 2 * 2 * 2 * 3
 
 
-@pytest.mark.parametrize("gname", GRAPHS)
+@pytest.mark.parametrize("gname", GRAPHS + FALLBACK)
 def test_plan_invariants(gname):
     for call, p in zip(CALLS, plans(gname)):
         B = call[5]
@@ -102,6 +105,28 @@ def test_plan_invariants(gname):
         else:
             assert p["slab"] <= p["scratch"], (call, p)
     assert gname != "deg33" or all(p["name"] == "none" for p in plans(gname))
+
+
+@pytest.mark.parametrize("name", list(FALLBACK_KERNELS))
+def test_fallback_graphs_run_the_kernels_their_gpu_tests_name(name):
+    """Every call shape of tests/test_gpu_fallback.py: plain decodes of 24 / 32 / 264 frames up to 20
+    iterations and 20-iteration Monte-Carlo batches of 128, both algorithms, with and without
+    early stop.  The slab forms really keep messages in the slab (0 < lds_slots < E, or irr_S <
+    irr_P behind the <lds+slab> name) and cap the grid at one workgroup per CU."""
+    csr = fallback_csr(name)
+    E = csr[1].size
+    calls = [(algo, es, 0, 1, it, B) for algo in (0, 1) for es in (0, 1) for it in (1, 3, 5, 10, 20) for B in (24, 32, 264)]
+    calls += [(algo, es, 1, 0, 20, 128) for algo in (0, 1) for es in (0, 1)]
+    want = FALLBACK_KERNELS[name]
+    for call, p in zip(calls, bp_plans(csr, calls)):
+        assert p["name"] == want, (call, p)
+        if "gmem" in want or "slab" in want:
+            assert p["grid"] == min(call[5], 256) and p["slab"] > 0, (call, p)
+        else:
+            assert p["grid"] == call[5] and p["scratch"] == 0, (call, p)
+        if "gmem" in want:
+            assert 0 < p["lds_slots"] < E, (call, p)
+            assert p["scratch"] == p["grid"] * ((5 * E + 4 * (csr[2].size - 1) + 15) & ~15), (call, p)
 
 
 @pytest.mark.parametrize("gname", ["r36_1000", "r36_10000", "rsu_2000"])

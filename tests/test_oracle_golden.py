@@ -137,6 +137,59 @@ def test_oracle_spa_rule_saturated_inputs():
     assert np.array_equal(np.sign(got), np.sign(x))
 
 
+def test_oracle_spa_f32_form_overflows_from_degree_7():
+    """The known limit of algo 2, the fp32 elementary-symmetric form of the kernels' check degrees
+    <= 6: its sums reach 2^(23 k) over k inputs, so six inputs near saturation overflow fp32 and
+    no output is finite -- NaN, or inf that the variable sums turn into inf - inf = NaN posteriors
+    (d = 7, x = 16: e_6 = e^96 > FLT_MAX).  Degree 6 is its last safe degree; algo 3, the
+    rescaled form the kernels use above it, has no such limit."""
+    want6 = 2 * np.arctanh(np.tanh(23 * np.log(2) / 2) ** 5)
+    np.testing.assert_allclose(oracle.check_update(np.full(6, 16.0, np.float32), 2), want6, rtol=1e-6)
+    for d, x in ((7, 16.0), (16, 8.0), (32, 4.0)):
+        v = np.full(d, x, np.float32)
+        bad = oracle.check_update(v, 2)  # inf / inf = NaN where both sums overflow, inf where one does
+        assert not np.isfinite(bad).any() and np.isnan(bad).any(), (d, x, bad)
+        np.testing.assert_allclose(oracle.check_update(v, 3), _spa_float64(v), rtol=1e-5)
+
+
+def test_oracle_spa_rescaled_f32_rule_vs_double_rule():
+    """algo 3 (the rescaled fp32 form of check degrees 7-32, csrc/bp_device.hpp) against algo 0,
+    degrees 2-32, magnitudes up to 60 nats: always finite and within the sum-product tolerance
+    of tests/test_gpu_fallback.py, 1e-4 + 1e-4 |c| -- random vectors, zeros, and every input
+    saturated with all-equal, alternating and random signs."""
+    rng = np.random.default_rng(11)
+    worst = 0.0
+    for d in range(2, 33):
+        xs = [(rng.normal(size=d) * rng.choice([0.1, 0.5, 2.0, 5.0, 20.0, 60.0])).astype(np.float32) for _ in range(200)]
+        for x in xs[:20]:
+            x[rng.integers(d)] = np.float32(0.0)
+        sat = np.full(d, 40.0, np.float32)
+        xs += [sat, -sat, sat * np.where(np.arange(d) % 2, -1, 1).astype(np.float32),
+               sat * rng.choice([-1.0, 1.0], size=d).astype(np.float32),
+               (rng.choice([-1.0, 1.0], size=d) * rng.uniform(15.0, 17.0, size=d)).astype(np.float32)]
+        for x in xs:
+            got = oracle.check_update(x, 3).astype(np.float64)
+            want = oracle.check_update(x, 0).astype(np.float64)
+            assert np.all(np.isfinite(got)), (d, x, got)
+            err = np.abs(got - want)
+            assert np.all(err <= 1e-4 + 1e-4 * np.abs(want)), (d, x, got, want)
+            worst = max(worst, float(err.max()))
+    print("algo 3 vs algo 0: max |delta| = %.3g nats" % worst)
+    # all terms positive: num and den each carry <= d roundings, so the ratio is good to 2 d = 64
+    # ulps (3.8e-6 in its logarithm), plus logf's and the fp32 result's ulp of a value <= 16
+    # (1.9e-6); measured 1.3e-6
+    assert worst < 6e-6
+
+
+def test_oracle_spa_f32_forms_agree_below_degree_7():
+    """Where both fp32 forms are defined (d <= 6) they differ by rounding only."""
+    rng = np.random.default_rng(12)
+    for _ in range(2000):
+        d = int(rng.integers(2, 7))
+        x = (rng.normal(size=d) * rng.choice([0.5, 5.0, 40.0])).astype(np.float32)
+        np.testing.assert_allclose(oracle.check_update(x, 3), oracle.check_update(x, 2), rtol=1e-5, atol=1e-5)
+
+
 @pytest.mark.parametrize("alpha", [1.0, 0.75, 0.8125])
 def test_oracle_minsum_rule_vs_float64(alpha):
     """Normalized min-sum: c_j = alpha * min_{i != j} |x_i| * prod_{i != j} sign(x_i), with
