@@ -76,6 +76,9 @@ def lib():
         "ldpc_sample_regular_dev": ([i, i, i, u64, u64, i, P, P, P, P], i),
         "ldpc_sample_regular": ([i, i, i, u64, u64, i, P, P, P], i),
         "ldpc_mc_ensemble_batch_dev": ([i, i, i, i, f, u64, u64, i, i, i, i64, P, P], i),
+        "ldpc_bp_ensemble_decode_dev": ([i, i, i, P, P, P, i, i, i, f, i, P, P, P, P], i),
+        "ldpc_mc_ensemble_soft_batch_dev": ([i, i, i, i, f, i, f, i, u64, u64, i, i, i, i64, P, P], i),
+        "ldpc_debug_ens_plan": ([i, i, i, i, P, i, P, P], i),
         "ldpc_sample_csr_dev": ([i, i, P, P, u64, u64, i, P, P, P, P], i),
         "ldpc_sample_csr": ([i, i, P, P, u64, u64, i, P, P, P], i),
         "ldpc_ml_decode_batch_dev": ([P, P, i, P, P, P], i),
@@ -112,4 +115,5 @@ def exported_symbols():
             "ldpc_sample_regular", "ldpc_mc_ensemble_batch_dev", "ldpc_ml_decode_batch_dev", "ldpc_ml_decode_batch",
             "ldpc_ml_ensemble_decode_dev", "ldpc_mc_ml_batch_dev", "ldpc_sample_csr_dev", "ldpc_sample_csr",
             "ldpc_mc_run", "ldpc_mc_run_csr", "ldpc_debug_loc_variant", "ldpc_debug_mc_plan",
-            "ldpc_debug_seq_stats", "ldpc_debug_peel_stats", "ldpc_debug_peel_cap"]
+            "ldpc_debug_seq_stats", "ldpc_debug_peel_stats", "ldpc_debug_peel_cap",
+            "ldpc_bp_ensemble_decode_dev", "ldpc_mc_ensemble_soft_batch_dev", "ldpc_debug_ens_plan"]

@@ -169,7 +169,7 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
             slab_per_wg = generic_msg_bytes(g);
             break;
         }
-        case BpPath::None: return p;
+        default: return p;  // None (choose_path never gives an Ens* path: those are bp_ens_plan's)
     }
     p.slab = slab_per_wg * (size_t)p.grid;
     p.scratch = p.slab;
@@ -177,6 +177,43 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
         p.counter = (long)p.slab;
         p.scratch += sizeof(uint32_t);
     }
+    return p;
+}
+
+// bp_ens_kernel: the shape alone decides (every graph of the batch is (dv, dc) regular on n
+// variables).  algo, early stop and want_post select the instantiation, not the layout.
+BpPlan bp_ens_plan(int n, int dv, int dc, int B, int iters, int /*algo*/, bool /*early_stop*/, bool mc,
+                   bool /*want_post*/, int cus) {
+    BpPlan p;
+    if (n <= 0 || dv <= 0 || dc <= 1 || dc > 32) return p;
+    const size_t E = (size_t)n * (size_t)dv;
+    const size_t block = ens_block_bytes((size_t)n, E), syn = ens_syn_bytes(E / (size_t)dc);
+    const bool lds = block + syn + (mc ? (size_t)(iters + 1) * 4 : 0) <= kLdsMax - 2048;
+    const int w = dc <= 8 ? 0 : (dc <= 16 ? 1 : 2);
+    static const BpPath paths[2][3] = {{BpPath::EnsG8, BpPath::EnsG16, BpPath::EnsG32},
+                                       {BpPath::Ens8, BpPath::Ens16, BpPath::Ens32}};
+    static const char *const names[2][3] = {{"bp_ens_kernel<8,gmem>", "bp_ens_kernel<16,gmem>", "bp_ens_kernel<32,gmem>"},
+                                            {"bp_ens_kernel<8,lds>", "bp_ens_kernel<16,lds>", "bp_ens_kernel<32,lds>"}};
+    // one workgroup per CU striding over the batch: under early stop frames end at different
+    // iterations, and the slabs of a gmem grid stay as few as the device can run at once
+    p.grid = std::min(B, std::min(cus, LDPC_GMEM_GRID));
+    size_t slab_per_wg = 0;
+    if (lds) {
+        p.threads = 256;
+        p.lds = block + syn + (mc ? (size_t)(iters + 1) * 4 : 0);
+    } else {
+        p.threads = LDPC_GMEM_T;
+        p.lds = (mc ? pad16((size_t)(iters + 1) * 4) : 0) + syn;  // the curve, the syndrome bits
+        if (p.lds > kLdsMax - 4096) return BpPlan();              // no room for those alone: no kernel
+        const size_t room = kLdsMax - 4096 - p.lds;
+        p.lds_slots = LDPC_GMEM_HYB ? (int)std::min<size_t>(E, room / 4) : 0;
+        p.lds += (size_t)p.lds_slots * 4;
+        slab_per_wg = block;
+    }
+    p.path = paths[lds][w];
+    p.name = names[lds][w];
+    p.slab = slab_per_wg * (size_t)p.grid;
+    p.scratch = p.slab;
     return p;
 }
 

@@ -575,6 +575,91 @@ int ldpc_mc_ensemble_batch_dev(int n, int dv, int dc, int channel, float param, 
     return LDPC_OK;
 }
 
+// --------------------------- ensemble soft decoding / MC -------------------
+// The shape and mode checks the two ensemble soft entries share; LDPC_EUNSUP when no
+// bp_ens_kernel covers the check degree.
+static int ens_soft_check(int n, int dv, int dc, int algo) {
+    LDPC_TRY(check_regular_shape(n, dv, dc));
+    LDPC_REQUIRE(algo == LDPC_ALGO_SPA || algo == LDPC_ALGO_MINSUM, "algo must be LDPC_ALGO_SPA or LDPC_ALGO_MINSUM");
+    if (bp_ens_plan(n, dv, dc, 1, 1, algo, false, false, true, 256).path == BpPath::None) {
+        set_error("no ensemble soft kernel for this shape (check degree > 32)");
+        return LDPC_EUNSUP;
+    }
+    return LDPC_OK;
+}
+
+// The launch plans (bp_ens_plan) of `count` ensemble soft-decoding calls on the (n, dv, dc)
+// shape, host only; calls / out / names as ldpc_debug_bp_plan.  LDPC_EUNSUP (after filling
+// out and names) when a call has no kernel.
+int ldpc_debug_ens_plan(int n, int dv, int dc, int count, const int32_t *calls, int cus, int64_t *out, char *names) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
+    LDPC_TRY(check_regular_shape(n, dv, dc));
+    bool none = false;
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 6 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        const BpPlan p = bp_ens_plan(n, dv, dc, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus);
+        int64_t *o = out + 9 * (size_t)i;
+        o[0] = (int64_t)p.path; o[1] = p.threads; o[2] = p.grid; o[3] = (int64_t)p.lds; o[4] = p.lds_slots;
+        o[5] = p.persistent; o[6] = (int64_t)p.slab; o[7] = p.counter; o[8] = (int64_t)p.scratch;
+        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+        none |= p.path == BpPath::None;
+    }
+    if (none) {
+        set_error("no ensemble soft kernel for this call (check degree > 32, or a curve beyond LDS)");
+        return LDPC_EUNSUP;
+    }
+    return LDPC_OK;
+}
+
+int ldpc_bp_ensemble_decode_dev(int n, int dv, int dc, const int32_t *d_check_lookup, const int32_t *d_variable_lookup,
+                                const float *d_llr, int B, int max_iters, int algo, float alpha, int early_stop,
+                                float *d_post, uint8_t *d_hard, int32_t *d_its, void *stream) {
+    LDPC_REQUIRE((B == 0 || (d_check_lookup && d_variable_lookup && d_llr)) && B >= 0 && max_iters >= 0,
+                 "bad ensemble soft batch arguments");
+    LDPC_TRY(ens_soft_check(n, dv, dc, algo));
+    LDPC_TRY(require_device());
+    if (B == 0) return LDPC_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    Workspace &ws = workspace(stream);
+    std::lock_guard<std::mutex> wl(ws.mu);
+    const size_t sb = ens_scratch_bytes(n, dv, dc, B, max_iters, algo, early_stop != 0, false, d_post != nullptr);
+    float *scratch = sb ? ws.scratch.get<float>((sb + 3) / 4) : nullptr;
+    LDPC_ALLOCATED(!sb || scratch);
+    LDPC_HIP(launch_ens_decode(n, dv, dc, d_check_lookup, d_variable_lookup, d_llr, B, max_iters, algo, alpha,
+                               early_stop, d_post, d_hard, d_its, static_cast<hipStream_t>(stream), scratch,
+                               sb ? ws.scratch.cap : 0));
+    return LDPC_OK;
+}
+
+int ldpc_mc_ensemble_soft_batch_dev(int n, int dv, int dc, int channel, float param, int algo, float alpha,
+                                    int early_stop, uint64_t seed, uint64_t first_cw, int B, int max_iters,
+                                    int expurgation, int64_t stop_frame_errors, int64_t *d_counters, void *stream) {
+    if (channel == LDPC_CH_BEC)  // exact erasure decoding: algo, alpha and early_stop do not apply
+        return ldpc_mc_ensemble_batch_dev(n, dv, dc, channel, param, seed, first_cw, B, max_iters, expurgation,
+                                          stop_frame_errors, d_counters, stream);
+    LDPC_REQUIRE(d_counters && B >= 0 && max_iters >= 0, "bad MC arguments");
+    float p, p2;
+    LDPC_TRY(channel_params(channel, param, &p, &p2));
+    LDPC_TRY(ens_soft_check(n, dv, dc, algo));
+    LDPC_TRY(require_device());
+    if (B == 0) return LDPC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only: devices launch in parallel
+    std::lock_guard<std::mutex> wl(ws.mu);
+    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
+    int32_t *cut = ws.cutoff.get<int32_t>(4), *chk = nullptr, *var = nullptr;
+    const size_t sb = ens_scratch_bytes(n, dv, dc, B, max_iters, algo, early_stop != 0, true, false);
+    float *scratch = sb ? ws.scratch.get<float>((sb + 3) / 4) : nullptr;
+    LDPC_ALLOCATED(trial && its && cut && (!sb || scratch));
+    // trial t: graph t (key = seed) and channel word t, as the BEC form
+    LDPC_TRY(sample_regular_locked(ws, n, dv, dc, seed, first_cw, B, chk, var, nullptr, s));
+    LDPC_HIP(launch_mc_ens(n, dv, dc, chk, var, channel, p, p2, seed, first_cw, B, max_iters, algo, alpha, early_stop,
+                           trial, its, s, scratch, sb ? ws.scratch.cap : 0));
+    LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
+    return LDPC_OK;
+}
+
 // --------------------------- ML ("optimal") erasure decoding ---------------
 static int ml_check_shape(int n, int m) {
     LDPC_REQUIRE(m >= 1 && m <= 1000, "ML decoding supports 1 <= n-k <= 1000 checks");

@@ -48,6 +48,24 @@ struct BpArgs {
     uint32_t *work;  // bp_loc_kernel early stop (persistent grid): next-codeword counter (zeroed per launch)
 };
 
+// bp_ens_kernel: codeword b on graph b (rows b of the sampler's lists; cptr / vptr implicit)
+struct EnsArgs {
+    const int32_t *chk, *var;  // [B][E] slot c*dc + j -> variable; edge v*dv + i -> check, ascending
+    int n, m, dv, dc, E, B;
+    const float *llr;
+    float *post;
+    uint8_t *hard;
+    int32_t *its;
+    int max_iters;
+    float alpha;
+    // Monte-Carlo mode
+    ChanArgs ch;
+    uint64_t first_cw;
+    int32_t *trial;  // [B][max_iters+1]
+    float *scratch;  // <*,gmem>: one ens_block_bytes slab per workgroup
+    int lds_slots;   // <*,gmem>: message slots [0, lds_slots) kept in LDS
+};
+
 inline ChanArgs make_chan(int kind, float p, float p2, uint64_t seed) {
     ChanArgs c;
     c.kind = kind;

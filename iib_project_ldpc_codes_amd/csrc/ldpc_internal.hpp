@@ -187,13 +187,17 @@ hipError_t launch_bp_decode(const ldpc_graph &g, const float *d_llr, int B, int 
 // The launch plan of one soft-decoding call (bp_plan.cpp): which kernel runs and everything the
 // launch needs, decided in one host-only function.  The launchers, the scratch sizing and the
 // kernel-name introspection all read it; nothing else re-derives these numbers.
-enum class BpPath { Loc, Lds36, Irr, Generic8, Generic16, Generic32, GenericG8, GenericG16, GenericG32, None };
+enum class BpPath {
+    Loc, Lds36, Irr, Generic8, Generic16, Generic32, GenericG8, GenericG16, GenericG32, None,
+    // bp_ens_kernel (bp_ens_plan only; listed after None so the values above stay as they were)
+    Ens8, Ens16, Ens32, EnsG8, EnsG16, EnsG32
+};
 struct BpPlan {
     BpPath path = BpPath::None;
     const char *name = "none";  // display name (ldpc_bp_kernel_name)
     int threads = 0, grid = 0;
     size_t lds = 0;             // dynamic LDS bytes
-    int lds_slots = 0;          // bp_generic_kernel<*,gmem>: message slots [0, lds_slots) kept in LDS
+    int lds_slots = 0;          // bp_generic_kernel / bp_ens_kernel <*,gmem>: message slots [0, lds_slots) kept in LDS
     bool persistent = false;    // bp_loc_kernel: the grid pulls codewords from a counter in scratch
     size_t slab = 0;            // bytes of per-workgroup slabs at the start of scratch (0: none)
     long counter = -1;          // byte offset of the work counter in scratch (-1: none)
@@ -202,6 +206,17 @@ struct BpPlan {
 // cus: compute units of the device (device_cus()); mc: fused-channel Monte-Carlo; want_post: a
 // decode that returns posteriors.
 BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post, int cus);
+// The plan of an ensemble call (bp_ens_kernel, bp_ens.hip): word b decodes on its own (dv, dc)
+// regular graph, rows b of the sampler's two lists.  One workgroup owns one block
+//   messages float[E] | channel LLRs float[n] | cross index int32[E]
+// (E = n dv; ens_block_bytes, 16-byte padded) -- in LDS when it fits there beside the early-stop
+// syndrome bits (ens_syn_bytes: two buffers of one bit per check, always in LDS) and the
+// Monte-Carlo curve, otherwise in a slab of the scratch buffer, one per workgroup of the grid,
+// with the first lds_slots messages kept in LDS.  dc > 32: BpPath::None.
+BpPlan bp_ens_plan(int n, int dv, int dc, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
+                   int cus);
+constexpr size_t ens_block_bytes(size_t n, size_t E) { return (E * 8 + n * 4 + 15) & ~(size_t)15; }
+constexpr size_t ens_syn_bytes(size_t m) { return (2 * ((m + 31) / 32) * 4 + 15) & ~(size_t)15; }
 // Compute units of the current device (256 when it cannot be queried), asked on every call:
 // devices launch from their own host threads, and the slabs and the grid must agree per device.
 int device_cus();
@@ -222,6 +237,20 @@ hipError_t launch_mc_decode(const ldpc_graph &g, int channel, float p, float p2,
 hipError_t launch_mc_reduce(const int32_t *trial, const int32_t *trial_its, int B, int max_iters,
                             int expurgation, int64_t stop_frame_errors, int64_t *d_counters,
                             int32_t *d_cutoff, hipStream_t stream);
+
+// Ensemble soft decoding (bp_ens.hip): word / trial b on graph b of (check_lookup, variable_lookup),
+// int32 [B][n*dv] each as launch_sample_regular writes them (a simple graph).  The lists are only
+// read.  Scratch: bp_ens_plan's; a shorter buffer is refused (hipErrorInvalidValue), a shape
+// without a kernel (check degree > 32) is hipErrorNotSupported.
+size_t ens_scratch_bytes(int n, int dv, int dc, int B, int iters, int algo, bool early_stop, bool mc, bool want_post);
+hipError_t launch_ens_decode(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
+                             const float *d_llr, int B, int max_iters, int algo, float alpha, int early_stop,
+                             float *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream, float *d_scratch,
+                             size_t scratch_bytes);
+hipError_t launch_mc_ens(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
+                         int channel, float p, float p2, uint64_t seed, uint64_t first_cw, int B, int max_iters,
+                         int algo, float alpha, int early_stop, int32_t *trial, int32_t *trial_its,
+                         hipStream_t stream, float *d_scratch, size_t scratch_bytes);
 
 // Buckets (= threads per workgroup) of the parallel graph sampler for n*dv
 // sockets; the permutation is in LDS (u16) when n*dv < 65536.  Must match

@@ -9,7 +9,7 @@
 //
 // Here: device slot r of round R decodes trials [(R*ndev + r)*batch, +batch) with
 // the fused channel + decode + counter kernels (ldpc_mc_batch_dev /
-// ldpc_mc_ensemble_batch_dev) on its own stream, launched from its own host thread;
+// ldpc_mc_ensemble_soft_batch_dev) on its own stream, launched from its own host thread;
 // per round ONE ncclAllReduce
 // (sum, int64) of [counter deltas | per-slot frame errors] over the devices
 // (RCCL, ncclCommInitAll; over xGMI on an MI355X node).  The stop rule is the
@@ -127,9 +127,10 @@ struct Run {
 
 int launch_batch(const Run &r, Slot &s, uint64_t first_cw, int B, int64_t stop, int64_t *d_counters) {
     if (B <= 0) return LDPC_OK;
-    if (r.ensemble)
-        return ldpc_mc_ensemble_batch_dev(r.n, r.dv, r.dc, r.channel, r.param, r.seed, first_cw, B, r.max_iters,
-                                          r.expurgation, stop, d_counters, s.stream);
+    if (r.ensemble)  // every channel (the BEC is forwarded to ldpc_mc_ensemble_batch_dev)
+        return ldpc_mc_ensemble_soft_batch_dev(r.n, r.dv, r.dc, r.channel, r.param, r.algo, r.alpha, r.early_stop,
+                                               r.seed, first_cw, B, r.max_iters, r.expurgation, stop, d_counters,
+                                               s.stream);
     return ldpc_mc_batch_dev(s.g, r.channel, r.param, r.seed, first_cw, B, r.max_iters, r.algo, r.alpha,
                              r.early_stop, r.expurgation, stop, d_counters, s.stream);
 }
@@ -373,8 +374,6 @@ int ldpc_mc_run(const int32_t *variable_to_check_list, const int32_t *check_to_v
     LDPC_TRY(check_common(channel, max_iters, batch, devices, ndev, counters));
     Run r;
     r.ensemble = (variable_to_check_list == nullptr && check_to_variable_list == nullptr);
-    LDPC_REQUIRE(!r.ensemble || channel == LDPC_CH_BEC,
-                 "ldpc_mc_run: ensemble mode (NULL edge lists) is defined for the BEC");
     LDPC_REQUIRE(r.ensemble || (variable_to_check_list && check_to_variable_list),
                  "ldpc_mc_run: give both edge lists (fixed code) or neither (ensemble)");
     r.v2c = variable_to_check_list;

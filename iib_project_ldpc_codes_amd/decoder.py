@@ -2,6 +2,7 @@
 
 * ``bec_decode``  -- message_passing.c:7-82 over a batch of words (bit-exact).
 * ``bp_decode``   -- flooding sum-product / normalized min-sum (new capability).
+* ``bp_ensemble_decode_dev`` -- the same decoders, word b on its own device-sampled graph b.
 * ``ml_decode``   -- ML ("optimal") erasure decoding, optimal_decode of
                      parallel_simulator.py:60-129 (GF(2) elimination on the device).
 * ``channel``     -- on-device BEC / BSC / BI-AWGN channel outputs (Philox).
@@ -150,6 +151,31 @@ def bp_decode(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False):
     post, hard, its = bp_decode_dev(graph, t, max_iters, algo, alpha, early_stop)
     torch.cuda.synchronize()
     return post.cpu().numpy(), hard.cpu().numpy(), its.cpu().numpy()
+
+
+def bp_ensemble_decode_dev(n, dv, dc, check_lookup, variable_lookup, llr, max_iters, algo="spa", alpha=1.0,
+                           early_stop=False, post=None, hard=None, its=None, stream=None, want_post=True,
+                           want_hard=True):
+    """Word b decoded on graph b: check_lookup / variable_lookup int32 [B, n*dv] device tensors
+    as graph.sample_device / ldpc_sample_regular_dev write them (simple graphs; only read), llr
+    float32 [B, n].  Returns (post, hard, its) device tensors."""
+    torch = _torch()
+    B = llr.shape[0]
+    assert llr.dtype == torch.float32 and llr.is_contiguous() and llr.shape[1] == n
+    for t in (check_lookup, variable_lookup):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B, n * dv)
+    if post is None and want_post:
+        post = torch.empty_like(llr)
+    if hard is None and want_hard:
+        hard = torch.empty(llr.shape, dtype=torch.uint8, device=llr.device)
+    if its is None:
+        its = torch.empty((B,), dtype=torch.int32, device=llr.device)
+    rc = _native.lib().ldpc_bp_ensemble_decode_dev(n, dv, dc, check_lookup.data_ptr(), variable_lookup.data_ptr(),
+                                                   llr.data_ptr(), B, max_iters, ALGOS[algo], float(alpha),
+                                                   int(bool(early_stop)), _ptr(post), _ptr(hard), _ptr(its),
+                                                   _stream(stream))
+    _native.check(rc, "ldpc_bp_ensemble_decode_dev")
+    return post, hard, its
 
 
 # ------------------------------------------------------------------ channels

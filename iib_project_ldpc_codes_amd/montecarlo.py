@@ -40,16 +40,24 @@ def device_executor(mc):
 
 def ensemble_executor(mc, n, dv, dc):
     """Batch executor for ensemble mode: trial t decodes on its own random (dv, dc)
-    graph t (ldpc_mc_ensemble_batch_dev; parallel_simulator.py:198-231 draws a fresh
-    code per trial)."""
+    graph t (parallel_simulator.py:198-231 draws a fresh code per trial):
+    ldpc_mc_ensemble_batch_dev on the BEC, ldpc_mc_ensemble_soft_batch_dev (mc.algo, mc.alpha,
+    mc.early_stop) on the BSC and BI-AWGN."""
     torch = mc.torch
 
     def run(first_cw, B, stop_frame_errors, counters, stream=None):
         s = stream if stream is not None else torch.cuda.current_stream()
-        rc = _native.lib().ldpc_mc_ensemble_batch_dev(n, dv, dc, mc.channel, mc.param, mc.seed, int(first_cw), int(B),
-                                                      mc.max_iters, mc.expurgation, int(stop_frame_errors),
-                                                      counters.data_ptr(), s.cuda_stream)
-        _native.check(rc, "ldpc_mc_ensemble_batch_dev")
+        if mc.channel == CHANNELS["bec"]:
+            rc = _native.lib().ldpc_mc_ensemble_batch_dev(n, dv, dc, mc.channel, mc.param, mc.seed, int(first_cw),
+                                                          int(B), mc.max_iters, mc.expurgation,
+                                                          int(stop_frame_errors), counters.data_ptr(), s.cuda_stream)
+            _native.check(rc, "ldpc_mc_ensemble_batch_dev")
+            return
+        rc = _native.lib().ldpc_mc_ensemble_soft_batch_dev(n, dv, dc, mc.channel, mc.param, mc.algo, mc.alpha,
+                                                           int(mc.early_stop), mc.seed, int(first_cw), int(B),
+                                                           mc.max_iters, mc.expurgation, int(stop_frame_errors),
+                                                           counters.data_ptr(), s.cuda_stream)
+        _native.check(rc, "ldpc_mc_ensemble_soft_batch_dev")
     return run
 
 
@@ -145,7 +153,8 @@ class MonteCarlo:
 
     @classmethod
     def ensemble(cls, n, dv, dc, channel, param, max_iters, **kw):
-        """Fresh random (dv, dc) code per trial (BEC; parallel_simulator.run_simulation)."""
+        """Fresh random (dv, dc) code per trial (parallel_simulator.run_simulation on the BEC;
+        "bsc" / "awgn" with algo, alpha and early_stop decode on bp_ens_kernel)."""
         return cls(_Ensemble(n, dv, dc), channel, param, max_iters, **kw)
 
     def run_batch(self, first_cw, B, stop_frame_errors=0, stream=None):

@@ -178,7 +178,8 @@ int ldpc_mc_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t se
  * process over the same trials whatever ndev is.
  *   Graph: the reference's edge lists (fixed code, built on every device) -- or
  *   both lists NULL for ensemble mode (a fresh random (dv, dc) code per trial,
- *   BEC only, parallel_simulator.py:215); ldpc_mc_run_csr takes a CSR graph
+ *   parallel_simulator.py:215: every channel, through
+ *   ldpc_mc_ensemble_soft_batch_dev); ldpc_mc_run_csr takes a CSR graph
  *   (irregular codes).
  *   counters (host) int64[LDPC_MC_NCOUNT + max_iters + 1], layout as
  *   ldpc_mc_batch_dev, overwritten; rounds (may be NULL) = rounds run.
@@ -235,11 +236,42 @@ int ldpc_sample_csr(int n, int m, const int32_t *var_ptr, const int32_t *check_p
  * Ensemble BEC Monte-Carlo batch (run_simulation, parallel_simulator.py:168-272;
  * expurgated :169-285): trial t = first_cw + b draws graph t and channel word t,
  * decodes with message_passing semantics and accumulates counters exactly as
- * ldpc_mc_batch_dev (expurgation, sequential stop rule).
+ * ldpc_mc_batch_dev (expurgation, sequential stop rule).  channel must be
+ * LDPC_CH_BEC; the other channels: ldpc_mc_ensemble_soft_batch_dev.
  */
 int ldpc_mc_ensemble_batch_dev(int n, int dv, int dc, int channel, float param, uint64_t seed,
                                uint64_t first_cw, int B, int max_iters, int expurgation,
                                int64_t stop_frame_errors, int64_t *d_counters, void *stream);
+
+/*
+ * Soft decoding over the ensemble (new; the soft twin of ldpc_ml_ensemble_decode_dev):
+ * word b of d_llr float[B*n] is decoded on graph b of d_check_lookup /
+ * d_variable_lookup, int32[B][n*dv] each in the ldpc_sample_regular_dev output
+ * layout.  Precondition: the lists are as the sampler writes them -- a simple
+ * (dv, dc)-regular graph, both lists naming the same edges, each variable's checks
+ * ascending; other lists give undefined decisions (never an access outside the
+ * buffers).  The lists are only read.  Outputs, the NULL rules, B = 0, max_iters = 0
+ * and early_stop as ldpc_bp_decode_batch_dev; one workgroup per word builds the
+ * graph's cross index itself (csrc/bp_ens.hip), so no host-side graph is prepared.
+ * Check degrees above 32: LDPC_EUNSUP.
+ */
+int ldpc_bp_ensemble_decode_dev(int n, int dv, int dc, const int32_t *d_check_lookup,
+                                const int32_t *d_variable_lookup, const float *d_llr, int B, int max_iters,
+                                int algo, float alpha, int early_stop, float *d_post, uint8_t *d_hard,
+                                int32_t *d_its, void *stream);
+
+/*
+ * Ensemble Monte-Carlo batch on any channel: trial t = first_cw + b draws graph t
+ * (ldpc_sample_regular law, key = seed) and channel word t, decodes with algo /
+ * alpha / early_stop (the fused BSC / BI-AWGN channel of ldpc_mc_batch_dev) and
+ * accumulates counters exactly as ldpc_mc_batch_dev (expurgation, sequential stop
+ * rule).  LDPC_CH_BEC forwards to ldpc_mc_ensemble_batch_dev (algo, alpha and
+ * early_stop are then ignored).
+ */
+int ldpc_mc_ensemble_soft_batch_dev(int n, int dv, int dc, int channel, float param, int algo, float alpha,
+                                    int early_stop, uint64_t seed, uint64_t first_cw, int B, int max_iters,
+                                    int expurgation, int64_t stop_frame_errors, int64_t *d_counters,
+                                    void *stream);
 
 /* ---------------------------------------------------------------------- */
 /* ML ("optimal") erasure decoding                        */
@@ -318,6 +350,18 @@ int ldpc_debug_irr_layout(const int32_t *check_ptr, const int32_t *check_var, co
 int ldpc_debug_loc_layout(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
                           const int32_t *var_slot, int n, int m, int T, int32_t *shape, int32_t *var, int32_t *pos,
                           int32_t *info);
+
+/*
+ * Host-only: the launch plans of `count` ensemble soft-decoding calls on the (n, dv, dc)
+ * shape (csrc/bp_plan.cpp bp_ens_plan).  calls[i] = {B, iters, algo, early_stop, mc,
+ * want_post}; out[i] int64[9] = {path, threads, grid, LDS bytes, lds_slots, 0, slab bytes, -1,
+ * scratch bytes}; names + 64 i: the kernel's display name, bp_ens_kernel<8|16|32,lds|gmem>.
+ * One workgroup owns pad16(8 n dv + 4 n) bytes (messages, channel LLRs, cross index): in LDS
+ * when that fits beside the early-stop syndrome bits and the Monte-Carlo curve, else one slab
+ * of scratch per workgroup of the grid.  LDPC_EUNSUP when a call has no kernel (dc > 32).
+ */
+int ldpc_debug_ens_plan(int n, int dv, int dc, int count, const int32_t *calls, int cus, int64_t *out,
+                        char *names);
 
 /*
  * Host-only: ldpc_mc_run's round accounting (csrc/mc_plan.hpp: per-slot batch clamp to

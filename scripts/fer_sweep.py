@@ -4,7 +4,9 @@
   cfg4: RSU rate-1/2 irregular (ring degree-2 placement, ensembles.py deg2="path"), n=20000,
         BI-AWGN, SPA, 100 it
   ens:  BASELINE configs[4] -- expurgated (3,6) ensemble (a fresh device-sampled graph per
-        trial, parallel_simulator_expurgated.py), n=64800, BEC, 200 it, expurgation X=3
+        trial, parallel_simulator_expurgated.py), n=64800, BEC, 200 it, expurgation X=3;
+        --channel bsc|awgn [--algo minsum|spa]: the same ensemble under soft decoding (50 it,
+        early stop, no expurgation unless --expurgation is given)
 One process per GPU: `--gpus N` starts the N ranks itself (decided before any HIP call, refused
 when fewer than N GPUs are visible -- iib_project_ldpc_codes_amd/launch.py, the same plan as
 bench.py), or runs as a rank of an external torchrun; trials shard by index, counters are
@@ -13,6 +15,7 @@ parallel_simulator.py:198), --trials, or --seconds.
 
   python scripts/fer_sweep.py cfg3 [--trials 1000000] [--seconds 60]
   python scripts/fer_sweep.py cfg4 --gpus 8 --seconds 300
+  python scripts/fer_sweep.py ens --channel bsc --algo minsum --points 0.07,0.065
 """
 import argparse
 import json
@@ -43,7 +46,11 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=11)
     ap.add_argument("--stop-errors", type=int, default=200)
     ap.add_argument("--deg2", default="path", help="cfg4 degree-2 placement (ensembles.sample_irregular)")
-    ap.add_argument("--expurgation", type=int, default=3, help="ens: X (parallel_simulator_expurgated.py argv[9])")
+    ap.add_argument("--expurgation", type=int, default=None,
+                    help="ens: X (parallel_simulator_expurgated.py argv[9]); default 3 on the BEC, none otherwise")
+    ap.add_argument("--channel", choices=["bec", "bsc", "awgn"], default="bec", help="ens: the channel")
+    ap.add_argument("--algo", choices=["spa", "minsum"], default=None,
+                    help="ens on bsc / awgn: the decoder (default minsum on bsc, spa on awgn)")
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks, one process per GPU (default: torchrun's WORLD_SIZE, else 1); "
                          "without WORLD_SIZE the sweep starts them itself")
@@ -52,6 +59,8 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.expurgation is None:
+        args.expurgation = 3 if args.channel == "bec" else -1
     return args
 
 
@@ -77,9 +86,15 @@ def main(argv=None):
         batch = args.batch or 65536
     elif args.config == "ens":
         g = None
-        channel, algo, alpha, iters = "bec", "spa", 1.0, 200
-        points = [float(p) for p in (args.points or "0.425,0.42").split(",")]
-        batch = args.batch or 16384
+        channel = args.channel
+        if channel == "bec":
+            algo, alpha, iters, default_points = "spa", 1.0, 200, "0.425,0.42"
+        else:
+            algo = args.algo or ("minsum" if channel == "bsc" else "spa")
+            alpha, iters = (0.75 if algo == "minsum" else 1.0), 50
+            default_points = "0.07,0.065" if channel == "bsc" else "0.86,0.84"
+        points = [float(p) for p in (args.points or default_points).split(",")]
+        batch = args.batch or (16384 if channel == "bec" else 4096)
     else:
         g = ensembles.sample_irregular(ensembles.RSU_DL4, 20000, seed=1, deg2=args.deg2)
         channel, algo, alpha, iters = "awgn", "spa", 1.0, 100
@@ -88,8 +103,8 @@ def main(argv=None):
     n, rate = (64800, 0.5) if g is None else (g.n, 1.0 - g.m / g.n)
     for p in points:
         if g is None:
-            mc = MonteCarlo.ensemble(n, 3, 6, channel, p, iters, expurgation=args.expurgation, seed=args.seed,
-                                     batch=batch)
+            mc = MonteCarlo.ensemble(n, 3, 6, channel, p, iters, algo=algo, alpha=alpha, early_stop=True,
+                                     expurgation=args.expurgation, seed=args.seed, batch=batch)
         else:
             mc = MonteCarlo(g, channel, p, iters, algo=algo, alpha=alpha, early_stop=True, seed=args.seed,
                             batch=batch)
