@@ -41,7 +41,7 @@ constexpr size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // messages | MC: per-iteration curve (16-byte padded) | min-sum MC: syndrome bits
 size_t loc_lds_bytes(const GraphShape &g, int iters, bool mc, bool syn) {
-    return pad16((size_t)std::max(g.loc_words + 64, g.n) * 4) + (mc ? pad16((size_t)(iters + 1) * 4) : 0) +
+    return pad16((size_t)std::max(g.loc_words + 64, g.n) * 4) + (mc ? curve_bytes(iters) : 0) +
            (syn ? (size_t)((g.m + 31) / 32) * 4 : 0);
 }
 // Early stop with posteriors on bp_loc_kernel: a VP x T float2 slab per workgroup
@@ -63,9 +63,19 @@ size_t lds36_bytes(const GraphShape &g, int iters, bool et, bool mc) {
 }
 
 // bp_generic_kernel: every message (fp32) and sign byte of a codeword, and the posteriors
-size_t generic_msg_bytes(const GraphShape &g) { return pad16((size_t)g.E * 5 + (size_t)g.n * 4); }
+size_t generic_msg_bytes(const GraphShape &g) { return generic_block_bytes((size_t)g.n, (size_t)g.E); }
 size_t generic_lds_bytes(const GraphShape &g, int iters, bool mc) {
     return generic_msg_bytes(g) + (mc ? (size_t)(iters + 1) * 4 : 0);
+}
+
+// bp_generic_kernel / bp_ens_kernel <*,gmem>: 1024-thread workgroups (the caller sets the grid
+// and the slab of each); LDS holds `fixed` bytes (the curve, the syndrome bits) and
+// the rest of the CU's LDS is filled with the first message slots.
+void gmem_plan(BpPlan &p, size_t fixed, size_t E) {
+    p.threads = LDPC_GMEM_T;
+    const size_t room = fixed < kLdsMax - 4096 ? kLdsMax - 4096 - fixed : 0;
+    p.lds_slots = LDPC_GMEM_HYB ? (int)std::min(E, room / 4) : 0;
+    p.lds = fixed + (size_t)p.lds_slots * 4;
 }
 
 // The lane layout is present exactly when lane_T != 0 and the irregular one exactly when
@@ -159,13 +169,8 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
             p.name = p.path == BpPath::GenericG8    ? "bp_generic_kernel<8,gmem>"
                      : p.path == BpPath::GenericG16 ? "bp_generic_kernel<16,gmem>"
                                                     : "bp_generic_kernel<32,gmem>";
-            p.threads = LDPC_GMEM_T;
             p.grid = std::min(B, LDPC_GMEM_GRID);
-            p.lds = mc ? pad16((size_t)(iters + 1) * 4) : 0;  // the curve
-            // fill the rest of the CU's LDS with the first message slots
-            const size_t room = p.lds < kLdsMax - 4096 ? kLdsMax - 4096 - p.lds : 0;
-            p.lds_slots = LDPC_GMEM_HYB ? (int)std::min<size_t>((size_t)g.E, room / 4) : 0;
-            p.lds += (size_t)p.lds_slots * 4;
+            gmem_plan(p, mc ? curve_bytes(iters) : 0, (size_t)g.E);
             slab_per_wg = generic_msg_bytes(g);
             break;
         }
@@ -202,12 +207,9 @@ BpPlan bp_ens_plan(int n, int dv, int dc, int B, int iters, int /*algo*/, bool /
         p.threads = 256;
         p.lds = block + syn + (mc ? (size_t)(iters + 1) * 4 : 0);
     } else {
-        p.threads = LDPC_GMEM_T;
-        p.lds = (mc ? pad16((size_t)(iters + 1) * 4) : 0) + syn;  // the curve, the syndrome bits
-        if (p.lds > kLdsMax - 4096) return BpPlan();              // no room for those alone: no kernel
-        const size_t room = kLdsMax - 4096 - p.lds;
-        p.lds_slots = LDPC_GMEM_HYB ? (int)std::min<size_t>(E, room / 4) : 0;
-        p.lds += (size_t)p.lds_slots * 4;
+        const size_t fixed = (mc ? curve_bytes(iters) : 0) + syn;  // the curve, the syndrome bits
+        if (fixed > kLdsMax - 4096) return BpPlan();               // no room for those alone: no kernel
+        gmem_plan(p, fixed, E);
         slab_per_wg = block;
     }
     p.path = paths[lds][w];

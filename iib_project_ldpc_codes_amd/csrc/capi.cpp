@@ -48,6 +48,21 @@ using OwnedGraph = std::unique_ptr<ldpc_graph, void (*)(ldpc_graph *)>;
         if (!(ptrs)) return LDPC_EHIP; \
     } while (0)
 
+// The workspace's scratch buffer grown to `bytes` (nullptr: none needed); false: allocation failed
+static bool get_scratch(Workspace &ws, size_t bytes, float *&scratch) {
+    scratch = bytes ? ws.scratch.get<float>((bytes + 3) / 4) : nullptr;
+    return !bytes || scratch;
+}
+
+// Row i of the debug plans: out + 9 i = {path, threads, grid, LDS bytes, lds_slots, persistent,
+// slab bytes, counter offset (-1: none), scratch bytes}; names + 64 i: the kernel's display name
+static void write_plan(const BpPlan &p, int i, int64_t *out, char *names) {
+    int64_t *o = out + 9 * (size_t)i;
+    o[0] = (int64_t)p.path; o[1] = p.threads; o[2] = p.grid; o[3] = (int64_t)p.lds; o[4] = p.lds_slots;
+    o[5] = p.persistent; o[6] = (int64_t)p.slab; o[7] = p.counter; o[8] = (int64_t)p.scratch;
+    snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+}
+
 extern "C" {
 
 const char *ldpc_last_error(void) { return g_err.c_str(); }
@@ -177,9 +192,7 @@ int ldpc_debug_loc_variant(const int32_t *check_ptr, const int32_t *check_var, c
 }
 
 // The launch plans (bp_plan) of `count` soft-decoding calls on one graph, from the host layouts
-// alone.  calls[i] = {B, iters, algo, early_stop, mc, want_post}; out[i] = {path, threads, grid,
-// LDS bytes, lds_slots, persistent, slab bytes, counter offset (-1: none), scratch bytes};
-// names + 64 i: the kernel's display name.
+// alone.  calls[i] = {B, iters, algo, early_stop, mc, want_post}; out / names: write_plan's rows.
 int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
                        const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
                        char *names) {
@@ -193,10 +206,7 @@ int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const
         const int32_t *c = calls + 6 * (size_t)i;
         LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
         const BpPlan p = bp_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus);
-        int64_t *o = out + 9 * (size_t)i;
-        o[0] = (int64_t)p.path; o[1] = p.threads; o[2] = p.grid; o[3] = (int64_t)p.lds; o[4] = p.lds_slots;
-        o[5] = p.persistent; o[6] = (int64_t)p.slab; o[7] = p.counter; o[8] = (int64_t)p.scratch;
-        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+        write_plan(p, i, out, names);
     }
     return LDPC_OK;
 }
@@ -286,8 +296,8 @@ static int bp_decode_locked(Workspace &ws, const ldpc_graph &g, const float *d_l
                             float alpha, int early_stop, float *d_post, uint8_t *d_hard, int32_t *d_its,
                             hipStream_t s) {
     const size_t sb = bp_scratch_bytes(g, B, max_iters, algo, early_stop != 0, false, d_post != nullptr);
-    float *scratch = sb ? ws.scratch.get<float>((sb + 3) / 4) : nullptr;
-    LDPC_ALLOCATED(!sb || scratch);
+    float *scratch;
+    LDPC_ALLOCATED(get_scratch(ws, sb, scratch));
     // no posteriors asked for: early stop may take the hard-decision path (bp_loc_kernel)
     LDPC_HIP(launch_bp_decode(g, d_llr, B, max_iters, algo, alpha, early_stop, d_post, d_hard, d_its, s, scratch,
                               ws.scratch.cap));
@@ -384,8 +394,8 @@ int ldpc_mc_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t se
     int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
     int32_t *cut = ws.cutoff.get<int32_t>(4);
     const size_t sb = channel != LDPC_CH_BEC ? bp_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, true, false) : 0;
-    float *scratch = sb ? ws.scratch.get<float>((sb + 3) / 4) : nullptr;
-    LDPC_ALLOCATED(trial && its && cut && (!sb || scratch));
+    float *scratch;
+    LDPC_ALLOCATED(trial && its && cut && get_scratch(ws, sb, scratch));
     LDPC_HIP(launch_mc_decode(*g, channel, p, p2, seed, first_cw, B, max_iters, algo, alpha, early_stop, trial, its,
                               s, scratch, sb ? ws.scratch.cap : 0));
     LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
@@ -599,10 +609,7 @@ int ldpc_debug_ens_plan(int n, int dv, int dc, int count, const int32_t *calls, 
         const int32_t *c = calls + 6 * (size_t)i;
         LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
         const BpPlan p = bp_ens_plan(n, dv, dc, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus);
-        int64_t *o = out + 9 * (size_t)i;
-        o[0] = (int64_t)p.path; o[1] = p.threads; o[2] = p.grid; o[3] = (int64_t)p.lds; o[4] = p.lds_slots;
-        o[5] = p.persistent; o[6] = (int64_t)p.slab; o[7] = p.counter; o[8] = (int64_t)p.scratch;
-        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+        write_plan(p, i, out, names);
         none |= p.path == BpPath::None;
     }
     if (none) {
@@ -624,8 +631,8 @@ int ldpc_bp_ensemble_decode_dev(int n, int dv, int dc, const int32_t *d_check_lo
     Workspace &ws = workspace(stream);
     std::lock_guard<std::mutex> wl(ws.mu);
     const size_t sb = ens_scratch_bytes(n, dv, dc, B, max_iters, algo, early_stop != 0, false, d_post != nullptr);
-    float *scratch = sb ? ws.scratch.get<float>((sb + 3) / 4) : nullptr;
-    LDPC_ALLOCATED(!sb || scratch);
+    float *scratch;
+    LDPC_ALLOCATED(get_scratch(ws, sb, scratch));
     LDPC_HIP(launch_ens_decode(n, dv, dc, d_check_lookup, d_variable_lookup, d_llr, B, max_iters, algo, alpha,
                                early_stop, d_post, d_hard, d_its, static_cast<hipStream_t>(stream), scratch,
                                sb ? ws.scratch.cap : 0));
@@ -650,8 +657,8 @@ int ldpc_mc_ensemble_soft_batch_dev(int n, int dv, int dc, int channel, float pa
     int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
     int32_t *cut = ws.cutoff.get<int32_t>(4), *chk = nullptr, *var = nullptr;
     const size_t sb = ens_scratch_bytes(n, dv, dc, B, max_iters, algo, early_stop != 0, true, false);
-    float *scratch = sb ? ws.scratch.get<float>((sb + 3) / 4) : nullptr;
-    LDPC_ALLOCATED(trial && its && cut && (!sb || scratch));
+    float *scratch;
+    LDPC_ALLOCATED(trial && its && cut && get_scratch(ws, sb, scratch));
     // trial t: graph t (key = seed) and channel word t, as the BEC form
     LDPC_TRY(sample_regular_locked(ws, n, dv, dc, seed, first_cw, B, chk, var, nullptr, s));
     LDPC_HIP(launch_mc_ens(n, dv, dc, chk, var, channel, p, p2, seed, first_cw, B, max_iters, algo, alpha, early_stop,

@@ -216,6 +216,10 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop,
 BpPlan bp_ens_plan(int n, int dv, int dc, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
                    int cus);
 constexpr size_t ens_block_bytes(size_t n, size_t E) { return (E * 8 + n * 4 + 15) & ~(size_t)15; }
+// bp_generic_kernel's block: messages float[E] | channel LLRs float[n] | decision bytes u8[E]
+constexpr size_t generic_block_bytes(size_t n, size_t E) { return (E * 5 + n * 4 + 15) & ~(size_t)15; }
+// The Monte-Carlo curve (iters + 1 counts) where something follows it in LDS: 16-byte padded
+constexpr size_t curve_bytes(int iters) { return ((size_t)(iters + 1) * 4 + 15) & ~(size_t)15; }
 constexpr size_t ens_syn_bytes(size_t m) { return (2 * ((m + 31) / 32) * 4 + 15) & ~(size_t)15; }
 // Compute units of the current device (256 when it cannot be queried), asked on every call:
 // devices launch from their own host threads, and the slabs and the grid must agree per device.

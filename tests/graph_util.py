@@ -104,7 +104,7 @@ def extreme_llrs(n, B, seed):
 FALLBACK_KERNELS = {
     "r48_256": "bp_irr_kernel<lds>",            # DC = 8, every message in LDS
     "r48_9216": "bp_irr_kernel<lds+slab>",      # DC = 8, rows beyond LDS in the slab
-    "r58_320": "bp_generic_kernel<8,lds>",      # variable degree 5 > kGenDV: the looped variable branch
+    "r58_320": "bp_generic_kernel<8,lds>",      # variable degree 5 > kFloodDV: the looped variable branch
     "r58_8800": "bp_generic_kernel<8,gmem>",    # E = 44,000 > 39,936 LDS slots: messages in the slab
     "r510_640": "bp_generic_kernel<16,lds>",
     "r510_9000": "bp_generic_kernel<16,gmem>",  # E = 45,000
@@ -127,10 +127,15 @@ def fallback_csr(name):
         deg = deg[np.random.default_rng(5).permutation(deg.size)]  # degree classes interleaved
         cptr, cvar = mixed_checks(deg, n, seed=1)
         return csr_from_checks(cptr, cvar, n)
+    g = fallback_regular(name)
+    return csr_from_checks(np.arange(g.m + 1) * g.dc, g.check_lookup, g.n)
+
+
+def fallback_regular(name):
+    """The graph of a regular FALLBACK_KERNELS name r<dv><dc>_<n>, in the reference's list format."""
     kind, n = name.split("_")
     dv, dc = _REGULAR[kind]
-    g = regular_simple(int(n), dv, dc, seed=1)
-    return csr_from_checks(np.arange(g.m + 1) * dc, g.check_lookup, g.n)
+    return regular_simple(int(n), dv, dc, seed=1)
 
 
 def csr_from_checks(cptr, cvar, n):
