@@ -41,54 +41,59 @@ def _load():
     return ct.CDLL(LIB_PATH, mode=ct.RTLD_GLOBAL)
 
 
+# Every entry point of the C ABI: name -> (argument types, result type)
+P, i, f, u64, i64 = ct.c_void_p, ct.c_int, ct.c_float, ct.c_uint64, ct.c_int64
+SIGNATURES = {
+    "message_passing": ([P, i, P, P, P, i, i, i, i], i),
+    "ldpc_graph_create": ([P, P, i, i, i, i, ct.POINTER(P)], i),
+    "ldpc_graph_create_csr": ([P, P, P, P, i, i, ct.POINTER(P)], i),
+    "ldpc_graph_destroy": ([P], None),
+    "ldpc_graph_info": ([P, P, P, P], i),
+    "ldpc_bec_decode_batch": ([P, P, i, i, i, i, P, i, i, P, P], i),
+    "ldpc_bec_decode_batch_dev": ([P, P, i, i, P, P, P], i),
+    "ldpc_bp_decode_batch": ([P, P, i, i, i, i, P, i, i, i, f, i, P, P, P], i),
+    "ldpc_bp_decode_batch_dev": ([P, P, i, i, i, f, i, P, P, P, P], i),
+    "ldpc_channel_dev": ([i, f, u64, u64, i, i, P, P], i),
+    "ldpc_mc_batch_dev": ([P, i, f, u64, u64, i, i, i, f, i, i, i64, P, P], i),
+    "ldpc_last_error": ([], ct.c_char_p),
+    "ldpc_device_count": ([], i),
+    "ldpc_set_device": ([i], i),
+    "ldpc_sync": ([P], i),
+    "ldpc_bp_kernel_name": ([P, i], ct.c_char_p),
+    "ldpc_debug_lane_layout": ([P, P, i, i, i, i, P, P, P, P], i),
+    "ldpc_debug_irr_layout": ([P, P, P, P, i, i, P, P, P], i),
+    "ldpc_debug_loc_layout": ([P, P, P, P, i, i, i, P, P, P, P], i),
+    "ldpc_debug_loc_variant": ([P, P, P, P, i, i, i, P], i),
+    "ldpc_debug_mc_plan": ([P, i64, i64, i64, i, i, P], i),
+    "ldpc_debug_bp_plan": ([P, P, P, P, i, i, i, P, i, P, P], i),
+    "ldpc_debug_seq_stats": ([P, i], i),
+    "ldpc_debug_peel_stats": ([P, i], i),
+    "ldpc_debug_peel_cap": ([i], i),
+    "ldpc_sample_regular_dev": ([i, i, i, u64, u64, i, P, P, P, P], i),
+    "ldpc_sample_regular": ([i, i, i, u64, u64, i, P, P, P], i),
+    "ldpc_mc_ensemble_batch_dev": ([i, i, i, i, f, u64, u64, i, i, i, i64, P, P], i),
+    "ldpc_bp_ensemble_decode_dev": ([i, i, i, P, P, P, i, i, i, f, i, P, P, P, P], i),
+    "ldpc_mc_ensemble_soft_batch_dev": ([i, i, i, i, f, i, f, i, u64, u64, i, i, i, i64, P, P], i),
+    "ldpc_debug_ens_plan": ([i, i, i, i, P, i, P, P], i),
+    "ldpc_debug_bec_plan": ([i, i, i, i, P, P, P], i),
+    "ldpc_sample_csr_dev": ([i, i, P, P, u64, u64, i, P, P, P, P], i),
+    "ldpc_sample_csr": ([i, i, P, P, u64, u64, i, P, P, P], i),
+    "ldpc_ml_decode_batch_dev": ([P, P, i, P, P, P], i),
+    "ldpc_ml_decode_batch": ([P, P, i, P, P], i),
+    "ldpc_ml_ensemble_decode_dev": ([i, i, i, P, P, i, P, P, P], i),
+    "ldpc_mc_ml_batch_dev": ([P, i, i, i, f, u64, u64, i, i, i, i, i64, P, P, P], i),
+    "ldpc_mc_run": ([P, P, i, i, i, i, i, f, i, f, i, u64, i, i, i64, i64, i, ct.c_double, P, i, P, P], i),
+    "ldpc_mc_run_csr": ([P, P, P, P, i, i, i, f, i, f, i, u64, i, i, i64, i64, i, ct.c_double, P, i, P, P], i),
+}
+del P, i, f, u64, i64
+
+
 def lib():
     global _lib
     if _lib is not None:
         return _lib
     L = _load()
-    P, i, f, u64, i64 = ct.c_void_p, ct.c_int, ct.c_float, ct.c_uint64, ct.c_int64
-    sig = {
-        "message_passing": ([P, i, P, P, P, i, i, i, i], i),
-        "ldpc_graph_create": ([P, P, i, i, i, i, ct.POINTER(P)], i),
-        "ldpc_graph_create_csr": ([P, P, P, P, i, i, ct.POINTER(P)], i),
-        "ldpc_graph_destroy": ([P], None),
-        "ldpc_graph_info": ([P, P, P, P], i),
-        "ldpc_bec_decode_batch": ([P, P, i, i, i, i, P, i, i, P, P], i),
-        "ldpc_bec_decode_batch_dev": ([P, P, i, i, P, P, P], i),
-        "ldpc_bp_decode_batch": ([P, P, i, i, i, i, P, i, i, i, f, i, P, P, P], i),
-        "ldpc_bp_decode_batch_dev": ([P, P, i, i, i, f, i, P, P, P, P], i),
-        "ldpc_channel_dev": ([i, f, u64, u64, i, i, P, P], i),
-        "ldpc_mc_batch_dev": ([P, i, f, u64, u64, i, i, i, f, i, i, i64, P, P], i),
-        "ldpc_last_error": ([], ct.c_char_p),
-        "ldpc_device_count": ([], i),
-        "ldpc_set_device": ([i], i),
-        "ldpc_sync": ([P], i),
-        "ldpc_bp_kernel_name": ([P, i], ct.c_char_p),
-        "ldpc_debug_lane_layout": ([P, P, i, i, i, i, P, P, P, P], i),
-        "ldpc_debug_irr_layout": ([P, P, P, P, i, i, P, P, P], i),
-        "ldpc_debug_loc_layout": ([P, P, P, P, i, i, i, P, P, P, P], i),
-        "ldpc_debug_loc_variant": ([P, P, P, P, i, i, i, P], i),
-        "ldpc_debug_mc_plan": ([P, i64, i64, i64, i, i, P], i),
-        "ldpc_debug_bp_plan": ([P, P, P, P, i, i, i, P, i, P, P], i),
-        "ldpc_debug_seq_stats": ([P, i], i),
-        "ldpc_debug_peel_stats": ([P, i], i),
-        "ldpc_debug_peel_cap": ([i], i),
-        "ldpc_sample_regular_dev": ([i, i, i, u64, u64, i, P, P, P, P], i),
-        "ldpc_sample_regular": ([i, i, i, u64, u64, i, P, P, P], i),
-        "ldpc_mc_ensemble_batch_dev": ([i, i, i, i, f, u64, u64, i, i, i, i64, P, P], i),
-        "ldpc_bp_ensemble_decode_dev": ([i, i, i, P, P, P, i, i, i, f, i, P, P, P, P], i),
-        "ldpc_mc_ensemble_soft_batch_dev": ([i, i, i, i, f, i, f, i, u64, u64, i, i, i, i64, P, P], i),
-        "ldpc_debug_ens_plan": ([i, i, i, i, P, i, P, P], i),
-        "ldpc_sample_csr_dev": ([i, i, P, P, u64, u64, i, P, P, P, P], i),
-        "ldpc_sample_csr": ([i, i, P, P, u64, u64, i, P, P, P], i),
-        "ldpc_ml_decode_batch_dev": ([P, P, i, P, P, P], i),
-        "ldpc_ml_decode_batch": ([P, P, i, P, P], i),
-        "ldpc_ml_ensemble_decode_dev": ([i, i, i, P, P, i, P, P, P], i),
-        "ldpc_mc_ml_batch_dev": ([P, i, i, i, f, u64, u64, i, i, i, i, i64, P, P, P], i),
-        "ldpc_mc_run": ([P, P, i, i, i, i, i, f, i, f, i, u64, i, i, i64, i64, i, ct.c_double, P, i, P, P], i),
-        "ldpc_mc_run_csr": ([P, P, P, P, i, i, i, f, i, f, i, u64, i, i, i64, i64, i, ct.c_double, P, i, P, P], i),
-    }
-    for name, (args, res) in sig.items():
+    for name, (args, res) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res
@@ -108,12 +113,4 @@ def last_error():
 
 def exported_symbols():
     """Names the C ABI header declares (tests check they all resolve)."""
-    return ["message_passing", "ldpc_graph_create", "ldpc_graph_create_csr", "ldpc_graph_destroy",
-            "ldpc_graph_info", "ldpc_bec_decode_batch", "ldpc_bec_decode_batch_dev", "ldpc_bp_decode_batch",
-            "ldpc_bp_decode_batch_dev", "ldpc_channel_dev", "ldpc_mc_batch_dev", "ldpc_last_error",
-            "ldpc_device_count", "ldpc_set_device", "ldpc_sync", "ldpc_debug_lane_layout", "ldpc_debug_irr_layout", "ldpc_debug_loc_layout", "ldpc_bp_kernel_name", "ldpc_sample_regular_dev",
-            "ldpc_sample_regular", "ldpc_mc_ensemble_batch_dev", "ldpc_ml_decode_batch_dev", "ldpc_ml_decode_batch",
-            "ldpc_ml_ensemble_decode_dev", "ldpc_mc_ml_batch_dev", "ldpc_sample_csr_dev", "ldpc_sample_csr",
-            "ldpc_mc_run", "ldpc_mc_run_csr", "ldpc_debug_loc_variant", "ldpc_debug_mc_plan",
-            "ldpc_debug_seq_stats", "ldpc_debug_peel_stats", "ldpc_debug_peel_cap",
-            "ldpc_bp_ensemble_decode_dev", "ldpc_mc_ensemble_soft_batch_dev", "ldpc_debug_ens_plan"]
+    return list(SIGNATURES)

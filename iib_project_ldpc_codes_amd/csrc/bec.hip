@@ -3,7 +3,7 @@
 //
 // Reference behaviour restated here:
 //   message_passing.c:7-82         -> bec_kernel           (bit-exact)
-#include <algorithm>
+#include <atomic>
 
 #include "kernel_args.hpp"
 #include "ldpc_mi355x.h"
@@ -11,12 +11,6 @@
 namespace ldpc {
 namespace {
 
-#ifndef LDPC_BEC_BITS
-#define LDPC_BEC_BITS 1  // fixed-code BEC Monte-Carlo on the bit-sliced kernel when its planes fit LDS
-#endif
-#ifndef LDPC_BEC_DEC_BITS
-#define LDPC_BEC_DEC_BITS 1  // batch BEC decode (B >= 64) on the bit-sliced kernel when its planes fit LDS
-#endif
 // ===========================================================================
 // 1. BEC erasure decoding -- message_passing.c:7-82, bit-exact.
 //
@@ -508,153 +502,123 @@ __global__ __launch_bounds__(T) void bec_dec_bits_kernel(BecArgs a, int B) {
     }
 }
 
-size_t bec_lds_bytes(const ldpc_graph &g, int iters) {
-    return (size_t)((iters * 4 + 15) & ~15) + (size_t)((g.n + 15) & ~15) + (size_t)g.m;
-}
-
-template <bool MC>
-hipError_t run_bec(const ldpc_graph &g, BecArgs a, int B, hipStream_t stream) {
-    const size_t lds = bec_lds_bytes(g, a.max_iters);
-    if (lds > kLdsMax - 1024) return hipErrorInvalidValue;
-    if (B <= 0) return hipSuccess;
-    if (g.n >= 4096) {
-        auto k = bec_kernel<1024, MC>;
-        hipError_t e = allow_lds(k, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(B), dim3(1024), lds, stream, a);
-    } else {
-        auto k = bec_kernel<256, MC>;
-        hipError_t e = allow_lds(k, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(B), dim3(256), lds, stream, a);
-    }
+// ---------------------------------------------------------------------------
+// 2. Launchers.  bec_plan (bec_plan.cpp) names the kernel, its shape, grid and LDS; the code
+// below fills the arguments and launches that instantiation.
+// ---------------------------------------------------------------------------
+template <typename K, typename... A>
+hipError_t launch_planned(K kernel, const BecPlan &p, hipStream_t stream, const A &...args) {
+    hipError_t e = allow_lds(kernel, p.lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3(p.threads), p.lds, stream, args...);
     return hipGetLastError();
-}
-
-// The bit-sliced kernels: bec_mc_bits_kernel (DEC = false: fused channel, 8 codewords per plane
-// byte) and bec_dec_bits_kernel (DEC = true: words from memory, 4 per plane byte).  Plane word
-// (u32 x W words per variable, or u8 for graphs whose u32 planes do not fit) and workgroup size
-// for this graph and batch; false when not even u8 planes fit.
-size_t bec_bits_lds_bytes(const ldpc_graph &g, bool dec, int W, int bytes_per_word) {
-    const int CW = dec ? 4 : 8, NB = CW * bytes_per_word * W;  // NB: codewords per workgroup
-    return ((((size_t)g.n + g.m) * W * bytes_per_word + 15) & ~(size_t)15) + (size_t)CW * NB + (dec ? 4 * W : 0) + 16;
-}
-bool bec_bits_shape(const ldpc_graph &g, bool dec, int B, int &W, int &T, int &bytes) {
-    T = g.n > 4096 ? 512 : 256;
-    bytes = 4;
-    if (dec && B < 64) return false;  // a few words (the drop-in's B = 1): one workgroup per codeword
-    for (int w : {4, 2, 1}) {
-        // enough workgroups to fill 256 CUs several times over, LDS for >= 2 per CU
-        const int NB = (dec ? 4 : 8) * 4 * w;
-        if (bec_bits_lds_bytes(g, dec, w, 4) <= 72 * 1024 && ((int64_t)B + NB - 1) / NB >= 1024) {
-            W = w;
-            return true;
-        }
-    }
-    W = 1;
-    if (bec_bits_lds_bytes(g, dec, 1, 4) <= kLdsMax - 4096) return true;
-    T = 1024;
-    bytes = 1;
-    return bec_bits_lds_bytes(g, dec, 1, 1) <= kLdsMax - 4096;
 }
 
 template <bool DEC, int T, int W, typename P>
-hipError_t launch_bec_bits_shape(const ldpc_graph &g, const BecArgs &a, int B, hipStream_t stream) {
-    const size_t lds = bec_bits_lds_bytes(g, DEC, W, (int)sizeof(P));
-    auto k = [] {
-        if constexpr (DEC) return bec_dec_bits_kernel<T, W, P>;
-        else return bec_mc_bits_kernel<T, W, P>;
-    }();
-    hipError_t e = allow_lds(k, lds);
-    if (e != hipSuccess) return e;
-    constexpr int NB = (DEC ? 4 : 8) * (int)sizeof(P) * W;
-    const unsigned grid = (unsigned)(((int64_t)B + NB - 1) / NB);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(T), lds, stream, a, B);
-    return hipGetLastError();
+hipError_t launch_bits_as(const BecPlan &p, const BecArgs &a, int B, hipStream_t stream) {
+    if constexpr (DEC) return launch_planned(bec_dec_bits_kernel<T, W, P>, p, stream, a, B);
+    else return launch_planned(bec_mc_bits_kernel<T, W, P>, p, stream, a, B);
 }
 
-// false: no bit-sliced shape for this call (the caller runs bec_kernel)
+// The bit-sliced instantiations: (threads, plane words per variable, plane word).  The kernels
+// lie in the code object in the order of these cases (and Decode's before Monte-Carlo's): it is
+// kept as it was measured.
+constexpr int bits_key(int T, int W, int plane) { return T * 100 + W * 10 + plane; }
 template <bool DEC>
-bool launch_bec_bits(const ldpc_graph &g, const BecArgs &a, int B, hipStream_t stream, hipError_t &e) {
-    int W = 0, T = 0, bytes = 0;
-    if (!bec_bits_shape(g, DEC, B, W, T, bytes)) return false;
-    if (bytes == 1) e = launch_bec_bits_shape<DEC, 1024, 1, uint8_t>(g, a, B, stream);
-    else if (T == 256 && W == 4) e = launch_bec_bits_shape<DEC, 256, 4, uint32_t>(g, a, B, stream);
-    else if (T == 256 && W == 2) e = launch_bec_bits_shape<DEC, 256, 2, uint32_t>(g, a, B, stream);
-    else if (T == 256) e = launch_bec_bits_shape<DEC, 256, 1, uint32_t>(g, a, B, stream);
-    else if (W == 4) e = launch_bec_bits_shape<DEC, 512, 4, uint32_t>(g, a, B, stream);
-    else if (W == 2) e = launch_bec_bits_shape<DEC, 512, 2, uint32_t>(g, a, B, stream);
-    else e = launch_bec_bits_shape<DEC, 512, 1, uint32_t>(g, a, B, stream);
-    return true;
+hipError_t launch_bits(const BecPlan &p, const BecArgs &a, int B, hipStream_t stream) {
+    switch (bits_key(p.threads, p.W, p.plane)) {
+        case bits_key(1024, 1, 1): return launch_bits_as<DEC, 1024, 1, uint8_t>(p, a, B, stream);
+        case bits_key(256, 4, 4): return launch_bits_as<DEC, 256, 4, uint32_t>(p, a, B, stream);
+        case bits_key(256, 2, 4): return launch_bits_as<DEC, 256, 2, uint32_t>(p, a, B, stream);
+        case bits_key(256, 1, 4): return launch_bits_as<DEC, 256, 1, uint32_t>(p, a, B, stream);
+        case bits_key(512, 4, 4): return launch_bits_as<DEC, 512, 4, uint32_t>(p, a, B, stream);
+        case bits_key(512, 2, 4): return launch_bits_as<DEC, 512, 2, uint32_t>(p, a, B, stream);
+        case bits_key(512, 1, 4): return launch_bits_as<DEC, 512, 1, uint32_t>(p, a, B, stream);
+        default: return hipErrorInvalidValue;  // a shape the plan does not give
+    }
 }
 
-BecArgs bec_args(const ldpc_graph &g) {
+template <bool MC>
+hipError_t launch_word(const BecPlan &p, const BecArgs &a, hipStream_t stream) {
+    return p.threads == 1024 ? launch_planned(bec_kernel<1024, MC>, p, stream, a)
+                             : launch_planned(bec_kernel<256, MC>, p, stream, a);
+}
+
+// MC: the fused-channel forms (bec_kernel<T, true>, bec_mc_bits_kernel).  hipErrorInvalidValue: no
+// kernel holds the graph (said before an empty batch is let through, as ever).
+template <bool MC>
+hipError_t launch_bec(const BecPlan &p, const BecArgs &a, int B, hipStream_t stream) {
+    switch (p.kernel) {
+        case MC ? BecKernel::McBits : BecKernel::DecBits: return launch_bits<!MC>(p, a, B, stream);
+        case BecKernel::Word: return B <= 0 ? hipSuccess : launch_word<MC>(p, a, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+BecArgs bec_args(int n, int m, int dv, int dc, int max_iters) {
     BecArgs a{};
+    a.n = n;
+    a.m = m;
+    a.dv = dv;
+    a.dc = dc;
+    a.max_iters = max_iters;
+    return a;
+}
+
+BecArgs bec_args(const ldpc_graph &g, int max_iters) {
+    BecArgs a = bec_args(g.n, g.m, g.dv, g.dc, max_iters);
     a.cvar = g.cvar;
     a.cptr = g.cptr;
     a.vptr = g.vptr;
     a.vchk = g.vchk;
-    a.n = g.n;
-    a.m = g.m;
-    a.dv = g.dv;
-    a.dc = g.dc;
     return a;
 }
+
+void mc_args(BecArgs &a, float p, float p2, uint64_t seed, uint64_t first_cw, int32_t *trial, int32_t *trial_its) {
+    a.ch = make_chan(0, p, p2, seed);
+    a.first_cw = first_cw;
+    a.trial = trial;
+    a.its = trial_its;
+}
+
+// Test-only bound on the peeling decoder's frontier capacity (ldpc_debug_peel_cap); 0: none.
+std::atomic<int> g_peel_cap{0};
 
 }  // namespace
 
 hipError_t launch_bec_decode(const ldpc_graph &g, uint8_t *d_words, int B, int max_iters,
                              int32_t *d_errors, int32_t *d_its, hipStream_t stream) {
-    BecArgs a = bec_args(g);
+    BecArgs a = bec_args(g, max_iters);
     a.words = d_words;
     a.errors = d_errors;
     a.its = d_its;
-    a.max_iters = max_iters;
-    hipError_t e = hipSuccess;
-    if (LDPC_BEC_DEC_BITS && launch_bec_bits<true>(g, a, B, stream, e)) return e;
-    return run_bec<false>(g, a, B, stream);
+    return launch_bec<false>(bec_plan(g.n, g.m, g.dc, B, max_iters, BecMode::Decode, 0), a, B, stream);
 }
 
 hipError_t launch_mc_bec(const ldpc_graph &g, float p, float p2, uint64_t seed, uint64_t first_cw, int B,
                          int max_iters, int32_t *trial, int32_t *trial_its, hipStream_t stream) {
-    BecArgs a = bec_args(g);
-    a.max_iters = max_iters;
-    a.ch = make_chan(0, p, p2, seed);
-    a.first_cw = first_cw;
-    a.trial = trial;
-    a.its = trial_its;
-    hipError_t e = hipSuccess;
-    if (LDPC_BEC_BITS && launch_bec_bits<false>(g, a, B, stream, e)) return e;
-    return run_bec<true>(g, a, B, stream);
+    BecArgs a = bec_args(g, max_iters);
+    mc_args(a, p, p2, seed, first_cw, trial, trial_its);
+    return launch_bec<true>(bec_plan(g.n, g.m, g.dc, B, max_iters, BecMode::Mc, 0), a, B, stream);
 }
 
 hipError_t launch_mc_bec_ensemble(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
                                   float p, uint64_t seed, uint64_t first_cw, int B, int max_iters, int32_t *trial,
                                   int32_t *trial_its, hipStream_t stream) {
     if (B <= 0) return hipSuccess;
-#ifndef LDPC_ENS_PEEL
-#define LDPC_ENS_PEEL 1  // ensemble MC on the frontier-peeling decoder (peel.hip) where it fits
-#endif
-    if (LDPC_ENS_PEEL) {
-        const hipError_t e = launch_mc_bec_peel(n, dv, dc, check_lookup, variable_lookup, p, seed, first_cw, B,
-                                                max_iters, trial, trial_its, stream);
-        if (e != hipErrorNotSupported) return e;
-    }
-    ldpc_graph g{};
-    g.n = n;
-    g.m = n * dv / dc;
-    g.dv = dv;
-    g.dc = dc;
-    BecArgs a = bec_args(g);
+    const int m = n * dv / dc;
+    const BecPlan plan = bec_plan(n, m, dc, B, max_iters, BecMode::EnsMc, g_peel_cap.load());
+    if (plan.kernel == BecKernel::Peel)
+        return launch_mc_bec_peel(plan, n, m, dv, dc, check_lookup, variable_lookup, p, seed, first_cw, max_iters,
+                                  trial, trial_its, stream);
+    BecArgs a = bec_args(n, m, dv, dc, max_iters);
     a.cvar = check_lookup;
     a.vchk = variable_lookup;
     a.graph_stride = (int64_t)n * dv;
-    a.max_iters = max_iters;
-    a.ch = make_chan(0, p, 0.0f, seed);
-    a.first_cw = first_cw;
-    a.trial = trial;
-    a.its = trial_its;
-    return run_bec<true>(g, a, B, stream);
+    mc_args(a, p, 0.0f, seed, first_cw, trial, trial_its);
+    return launch_bec<true>(plan, a, B, stream);
 }
+
+void peel_cap(int F) { g_peel_cap = F > 0 ? F : 0; }
 
 }  // namespace ldpc

@@ -211,6 +211,25 @@ int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const
     return LDPC_OK;
 }
 
+// The launch plans (bec_plan) of `count` BEC calls on an (n, m) graph of check degree dc (0:
+// irregular), from the shape alone.  calls[i] = {mode, B, iters, peel_cap}; out + 9 i = {kernel,
+// threads, W, plane bytes, codewords per workgroup, grid, LDS bytes, F, LDS cap}; names + 64 i:
+// the kernel's display name.  A call that no kernel holds is a row of its own (BecKernel::None).
+int ldpc_debug_bec_plan(int n, int m, int dc, int count, const int32_t *calls, int64_t *out, char *names) {
+    LDPC_REQUIRE(n > 0 && m > 0 && dc >= 0 && count >= 0 && (count == 0 || (calls && out && names)),
+                 "bad plan arguments");
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 4 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[0] <= 2 && c[1] >= 0 && c[2] >= 0, "bad plan arguments");
+        const BecPlan p = bec_plan(n, m, dc, c[1], c[2], static_cast<BecMode>(c[0]), c[3]);
+        int64_t *o = out + 9 * (size_t)i;
+        o[0] = (int64_t)p.kernel; o[1] = p.threads; o[2] = p.W; o[3] = p.plane; o[4] = p.cw_per_wg;
+        o[5] = p.grid; o[6] = (int64_t)p.lds; o[7] = p.F; o[8] = (int64_t)p.cap;
+        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+    }
+    return LDPC_OK;
+}
+
 const char *ldpc_bp_kernel_name(const ldpc_graph *g, int early_stop) {
     return g ? bp_kernel_name(*g, early_stop) : "none";
 }

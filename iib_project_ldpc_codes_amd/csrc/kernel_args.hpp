@@ -87,6 +87,11 @@ hipError_t launch_generic(const BpPlan &p, const ldpc_graph &g, BpArgs a, int al
 // BEC Monte-Carlo on a fixed code (bec.hip): launch_mc_decode's erasure-channel half
 hipError_t launch_mc_bec(const ldpc_graph &g, float p, float p2, uint64_t seed, uint64_t first_cw, int B,
                          int max_iters, int32_t *trial, int32_t *trial_its, hipStream_t stream);
+// Ensemble BEC Monte-Carlo by frontier peeling (peel.hip): launch_mc_bec_ensemble's BecKernel::Peel
+// plans; trial b decodes on the (dv, dc) regular graph b of the two lists.
+hipError_t launch_mc_bec_peel(const BecPlan &plan, int n, int m, int dv, int dc, const int32_t *check_lookup,
+                              const int32_t *variable_lookup, float p, uint64_t seed, uint64_t first_cw, int max_iters,
+                              int32_t *trial, int32_t *trial_its, hipStream_t stream);
 
 namespace {
 // Run-time (algo, early stop, Monte-Carlo) -> template arguments: f(int_c<ALGO>, bool_c<ET>, bool_c<MC>)

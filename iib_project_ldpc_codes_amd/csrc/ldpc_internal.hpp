@@ -1,4 +1,4 @@
-// Internal declarations shared by the host files (capi.cpp, graph_host.cpp, graph_device.cpp, bp_plan.cpp) and the kernels
+// Internal declarations shared by the host files (capi.cpp, graph_host.cpp, graph_device.cpp, bp_plan.cpp, bec_plan.cpp) and the kernels
 // (bec.hip, bp_*.hip, mc_kernels.hip, ml.hip, sampler.hip, peel.hip).  Not part of the public ABI (see include/ldpc_mi355x.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -148,7 +148,13 @@ inline bool lds_shape(int n, int &T, int &VPT) {
         if (1024L * v >= need) { VPT = v; return true; }
     return false;
 }
-constexpr size_t kLdsMax = 160 * 1024;  // LDS bytes of one CU (the launch plan and the BEC launchers budget against it)
+constexpr size_t kLdsMax = 160 * 1024;  // LDS bytes of one CU (the launch plans budget against it)
+// Dynamic-LDS caps of the BEC kernels (bec_plan.cpp): bec_kernel and bec_peel_kernel keep static
+// LDS (block_sum's partial sums, the list control words) beside the dynamic part; a bit-sliced
+// workgroup may fill the CU, and takes more than one word per variable only while two
+// workgroups still fit a CU.
+constexpr size_t kBecWordLdsCap = kLdsMax - 1024, kPeelLdsCap = kLdsMax - 1024;
+constexpr size_t kBecBitsLdsCap = kLdsMax - 4096, kBecBitsWideLdsCap = 72 * 1024;
 constexpr int kLdsDummy = 3 * 32 + 4;  // dummy message slots after the real ones (DV=3)
 
 // Message positions of the LDS-resident (3,6) kernel.  Checks are paired
@@ -167,8 +173,26 @@ namespace ldpc {
 
 void set_error(const std::string &msg);
 
+// The launch plan of one BEC call (bec_plan.cpp): which kernel runs and everything its launch
+// needs, decided in one host-only function; bec.hip and peel.hip launch what it says.
+enum class BecMode { Decode, Mc, EnsMc };  // words from memory | fixed code, fused channel | graph per trial
+enum class BecKernel { Word, DecBits, McBits, Peel, None };
+struct BecPlan {
+    BecKernel kernel = BecKernel::None;
+    const char *name = "none";  // display name, e.g. bec_dec_bits_kernel<256,2,u32>
+    int threads = 0;
+    int W = 0, plane = 0;    // bit-sliced: plane words per variable and bytes of one (4: u32, 1: u8)
+    int cw_per_wg = 0;       // codewords of one workgroup (1: bec_kernel, bec_peel_kernel)
+    int64_t grid = 0;
+    size_t lds = 0;          // dynamic LDS bytes
+    size_t cap = 0;          // the cap `lds` was admitted under (one of the four above)
+    int F = 0;               // bec_peel_kernel: entries of each frontier list
+};
+// dc: the check degree of a regular graph (read under EnsMc); peel_cap > 0: a test's bound on F (peel_cap()).
+BecPlan bec_plan(int n, int m, int dc, int B, int iters, BecMode mode, int peel_cap);
+
 // Kernel launchers (bec.hip, bp_dispatch.hip, mc_kernels.hip, ml.hip).  All asynchronous on `stream`.
-// Return hipSuccess or the launch error.
+// Return hipSuccess or the launch error; hipErrorInvalidValue when no kernel holds the graph.
 hipError_t launch_bec_decode(const ldpc_graph &g, uint8_t *d_words, int B, int max_iters,
                              int32_t *d_errors, int32_t *d_its, hipStream_t stream);
 
@@ -283,18 +307,14 @@ hipError_t launch_sample_csr(int n, int m, int E, const int32_t *d_vsock, const 
                              const int32_t *d_vptr, int max_cdeg, int max_vdeg, uint64_t seed, uint64_t first_graph,
                              int G, int32_t *check_var, int32_t *var_slot, int32_t *attempts, int max_attempts,
                              uint32_t *ctl, hipStream_t stream);
-// Frontier-peeling form of the ensemble BEC Monte-Carlo (peel.hip): regular (dv, dc) graphs
-// whose check state fits LDS; hipErrorNotSupported otherwise (launch_mc_bec_ensemble then
-// runs bec_kernel).
-hipError_t launch_mc_bec_peel(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
-                              float p, uint64_t seed, uint64_t first_cw, int B, int max_iters, int32_t *trial,
-                              int32_t *trial_its, hipStream_t stream);
-// Scan-path evidence of the peeling decoder (device global, this device): [0] overflowed
+// Scan-path evidence of the peeling decoder (peel.hip; device global, this device): [0] overflowed
 // iterations, [1] trials that overflowed, [2] trials decoded.
 hipError_t peel_stats(uint64_t *out, int reset);
-// Test-only cap on the frontier-list capacity (F > 0), 0 restores the LDS budget's capacity.
+// Test-only cap on the peeling decoder's frontier-list capacity (F > 0), 0 restores the LDS
+// budget's capacity.
 void peel_cap(int F);
-// BEC Monte-Carlo where trial b decodes on graph b of (check_lookup, variable_lookup).
+// BEC Monte-Carlo where trial b decodes on graph b of (check_lookup, variable_lookup): the
+// frontier-peeling decoder (peel.hip) where its check state fits LDS, else bec_kernel.
 hipError_t launch_mc_bec_ensemble(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
                                   float p, uint64_t seed, uint64_t first_cw, int B, int max_iters, int32_t *trial,
                                   int32_t *trial_its, hipStream_t stream);

@@ -18,10 +18,7 @@
 // iteration.  A frontier list that overflows its LDS capacity marks the next iteration for a
 // full scan (a frontier bitmap snapshot first, so no check is processed in the iteration its
 // count reached 1).
-#include "device_common.hpp"
-#include "ldpc_internal.hpp"
-
-#include <atomic>
+#include "kernel_args.hpp"
 
 namespace ldpc {
 namespace {
@@ -30,9 +27,6 @@ namespace {
 // the bitmap-snapshot scan because the frontier list overflowed, [1] trials with at least one
 // such iteration, [2] trials decoded (ldpc_debug_peel_stats).
 __device__ unsigned long long g_peel_stats[3];
-
-// Test-only frontier capacity override (ldpc_debug_peel_cap); 0 = the LDS budget's capacity.
-std::atomic<int> g_peel_cap{0};
 
 struct PeelArgs {
     const int32_t *cvar, *vchk;  // graph b at + b * graph_stride: check-major slots, v's checks
@@ -163,21 +157,10 @@ __global__ __launch_bounds__(T) void bec_peel_kernel(PeelArgs a) {
 
 }  // namespace
 
-// Bytes of LDS the peeling decoder needs with frontier lists of F entries each.
-static size_t peel_lds(int n, int m, int F) {
-    return (size_t)4 * (m + ((n + 31) >> 5) + ((m + 31) >> 5)) + (size_t)4 * F;
-}
-
-hipError_t launch_mc_bec_peel(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
-                              float p, uint64_t seed, uint64_t first_cw, int B, int max_iters, int32_t *trial,
-                              int32_t *trial_its, hipStream_t stream) {
-    const int m = n * dv / dc;
-    constexpr size_t kBudget = 160 * 1024 - 1024;  // the kernel's static LDS beside the dynamic part
-    if (m > 65536 || dc > 255 || (long)dc * n >= (1L << 24) || peel_lds(n, m, 256) > kBudget)
-        return hipErrorNotSupported;
-    if (B <= 0) return hipSuccess;
-    int F = (int)std::min<size_t>((size_t)m, (kBudget - peel_lds(n, m, 0)) / 4);
-    if (const int cap = g_peel_cap.load(); cap > 0) F = std::min(F, cap);
+// The plan (bec_plan.cpp) has admitted the shape and sized the frontier lists.
+hipError_t launch_mc_bec_peel(const BecPlan &plan, int n, int m, int dv, int dc, const int32_t *check_lookup,
+                              const int32_t *variable_lookup, float p, uint64_t seed, uint64_t first_cw, int max_iters,
+                              int32_t *trial, int32_t *trial_its, hipStream_t stream) {
     PeelArgs a;
     a.cvar = check_lookup;
     a.vchk = variable_lookup;
@@ -187,19 +170,14 @@ hipError_t launch_mc_bec_peel(int n, int dv, int dc, const int32_t *check_lookup
     a.dv = dv;
     a.dc = dc;
     a.max_iters = max_iters;
-    a.F = F;
-    a.ch.kind = 0;
-    a.ch.p = p;
-    a.ch.p2 = 0.0f;
-    a.ch.k0 = (uint32_t)seed;
-    a.ch.k1 = (uint32_t)(seed >> 32);
+    a.F = plan.F;
+    a.ch = make_chan(0, p, 0.0f, seed);
     a.first_cw = first_cw;
     a.trial = trial;
     a.its = trial_its;
-    const size_t lds = peel_lds(n, m, F);
-    hipError_t e = allow_lds(bec_peel_kernel<1024>, lds);
+    hipError_t e = allow_lds(bec_peel_kernel<1024>, plan.lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bec_peel_kernel<1024>, dim3(B), dim3(1024), lds, stream, a);
+    hipLaunchKernelGGL(bec_peel_kernel<1024>, dim3((unsigned)plan.grid), dim3(plan.threads), plan.lds, stream, a);
     return hipGetLastError();
 }
 
@@ -211,7 +189,5 @@ hipError_t peel_stats(uint64_t *out, int reset) {
     }
     return e;
 }
-
-void peel_cap(int F) { g_peel_cap = F > 0 ? F : 0; }
 
 }  // namespace ldpc

@@ -352,6 +352,17 @@ int ldpc_debug_loc_layout(const int32_t *check_ptr, const int32_t *check_var, co
                           int32_t *info);
 
 /*
+ * Host-only: the launch plans of `count` soft-decoding calls on one CSR graph (csrc/bp_plan.cpp
+ * bp_plan), from the host layouts alone; cus: compute units of the device planned for.
+ * calls[i] = {B, iters, algo, early_stop, mc, want_post}; out[i] int64[9] = {path, threads,
+ * grid, LDS bytes, lds_slots, persistent, slab bytes, counter offset (-1: none), scratch
+ * bytes}; names + 64 i: the kernel's display name.
+ */
+int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                       const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
+                       char *names);
+
+/*
  * Host-only: the launch plans of `count` ensemble soft-decoding calls on the (n, dv, dc)
  * shape (csrc/bp_plan.cpp bp_ens_plan).  calls[i] = {B, iters, algo, early_stop, mc,
  * want_post}; out[i] int64[9] = {path, threads, grid, LDS bytes, lds_slots, 0, slab bytes, -1,
@@ -362,6 +373,23 @@ int ldpc_debug_loc_layout(const int32_t *check_ptr, const int32_t *check_var, co
  */
 int ldpc_debug_ens_plan(int n, int dv, int dc, int count, const int32_t *calls, int cus, int64_t *out,
                         char *names);
+
+/*
+ * Host-only: the launch plans of `count` BEC erasure-decoding calls on a graph of n variables
+ * and m checks (csrc/bec_plan.cpp bec_plan); dc: the check degree of a regular graph, 0
+ * otherwise (only the ensemble mode reads it).  calls[i] = {mode, B, iters, peel_cap}: mode 0
+ * batch decode (words from memory), 1 fixed-code Monte-Carlo (fused channel), 2 ensemble
+ * Monte-Carlo (graph per trial); peel_cap > 0 bounds the frontier lists as
+ * ldpc_debug_peel_cap does.  out[i] int64[9] = {kernel, threads, W, plane bytes, codewords
+ * per workgroup, grid, dynamic LDS bytes, F, LDS cap}: kernel 0 bec_kernel, 1
+ * bec_dec_bits_kernel, 2 bec_mc_bits_kernel, 3 bec_peel_kernel, 4 none (the launch would
+ * fail; the other columns are 0); W plane words per variable of plane bytes each (4: u32, 1:
+ * u8; 0 for kernels 0 and 3); F the entries of each of bec_peel_kernel's frontier lists; LDS
+ * cap the bound the LDS bytes were admitted under.  names + 64 i: the display name,
+ * bec_kernel<T>, bec_dec_bits_kernel<T,W,u32|u8>, bec_mc_bits_kernel<T,W,u32|u8>,
+ * bec_peel_kernel<1024> or none.
+ */
+int ldpc_debug_bec_plan(int n, int m, int dc, int count, const int32_t *calls, int64_t *out, char *names);
 
 /*
  * Host-only: ldpc_mc_run's round accounting (csrc/mc_plan.hpp: per-slot batch clamp to

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A variant library that differs from the product build only in the flags of the decoder kernels'
-# files (KERNEL_SRCS in csrc/Makefile: the kernels and the launch plan that selects among them):
+# files (KERNEL_SRCS in csrc/Makefile: the kernels and the launch plans that select among them):
 #   scripts/build_kernel_variant.sh <name> [-DFLAG=...]  -> build_variants/<name>.so
 # (links the product objects of the other translation units: run `make` first)
 set -e

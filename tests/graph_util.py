@@ -173,3 +173,24 @@ def bp_plans(csr, calls, cus=256, env=None):
     for p, nm in zip(plans, names):
         p["name"] = nm.tobytes().split(b"\0")[0].decode()
     return plans
+
+
+BEC_DECODE, BEC_MC, BEC_ENS_MC = 0, 1, 2
+BEC_KERNELS = ("Word", "DecBits", "McBits", "Peel", "None")
+
+
+def bec_plans(n, m, calls, dc=6):
+    """The BEC decoders' launch plans (ldpc_debug_bec_plan, host only) of `calls` = (mode, B,
+    iters[, peel_cap]) tuples on a graph of n variables and m checks of degree dc."""
+    from iib_project_ldpc_codes_amd import _native
+    args = np.ascontiguousarray([tuple(c) + (0,) * (4 - len(c)) for c in calls], np.int32)
+    out = np.zeros((len(calls), 9), np.int64)
+    names = np.zeros((len(calls), 64), np.uint8)
+    rc = _native.lib().ldpc_debug_bec_plan(n, m, dc, len(calls), args.ctypes.data, out.ctypes.data, names.ctypes.data)
+    assert rc == 0, _native.last_error()
+    keys = ("kernel", "threads", "W", "plane", "cw_per_wg", "grid", "lds", "F", "cap")
+    plans = [dict(zip(keys, (int(x) for x in row))) for row in out]
+    for p, nm in zip(plans, names):
+        p["kernel"] = BEC_KERNELS[p["kernel"]]
+        p["name"] = nm.tobytes().split(b"\0")[0].decode()
+    return plans

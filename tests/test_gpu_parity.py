@@ -20,6 +20,7 @@ import pytest
 
 from oracle import oracle
 from tests.golden_util import load_bec_golden
+from tests.graph_util import BEC_DECODE, BEC_MC, bec_plans
 
 pytestmark = pytest.mark.gpu
 
@@ -212,16 +213,22 @@ def _perturbed_bec_batch(n, B, eps, iters, seed):
     return words, errin
 
 
-@pytest.mark.parametrize("n,B,eps,iters,csr", [
-    (1000, 65536, 0.42, 50, False),   # u32 planes, 4 words per variable (64 codewords per workgroup)
-    (1000, 32768, 0.40, 20, False),   # 2 words
-    (1000, 130, 0.45, 50, True),      # 1 word, CSR graph, partial last workgroup
-    (10000, 256, 0.42, 60, False),    # 512 threads
-    (64800, 72, 0.42, 200, False),    # u8 planes (4 codewords per byte)
-])
-def test_bec_bitsliced_batch_vs_oracle(torch, n, B, eps, iters, csr):
+# the last column, the kernel the plan names for the call, stays out of the test ids
+BEC_BITS_CASES = [
+    (1000, 65536, 0.42, 50, False, "bec_dec_bits_kernel<256,4,u32>"),
+    (1000, 32768, 0.40, 20, False, "bec_dec_bits_kernel<256,2,u32>"),
+    (1000, 130, 0.45, 50, True, "bec_dec_bits_kernel<256,1,u32>"),    # CSR graph, partial last workgroup
+    (10000, 256, 0.42, 60, False, "bec_dec_bits_kernel<512,1,u32>"),
+    (64800, 72, 0.42, 200, False, "bec_dec_bits_kernel<1024,1,u8>"),
+]
+
+
+@pytest.mark.parametrize("n,B,eps,iters,csr,kernel", BEC_BITS_CASES,
+                         ids=["-".join(map(str, c[:-1])) for c in BEC_BITS_CASES])
+def test_bec_bitsliced_batch_vs_oracle(torch, n, B, eps, iters, csr, kernel):
     from iib_project_ldpc_codes_amd import decoder
     from iib_project_ldpc_codes_amd.graph import TannerGraph
+    assert bec_plans(n, n // 2, [(BEC_DECODE, B, iters)])[0]["name"] == kernel
     g0 = TannerGraph.random_regular(n, 3, 6, seed=11)
     g = TannerGraph.from_csr(*g0.to_csr()) if csr else g0
     words, errin = _perturbed_bec_batch(n, B, eps, iters, seed=n + B)
@@ -485,15 +492,21 @@ def test_mc_bec_sequential_stop_rule(torch):
     np.testing.assert_array_equal(got, want)
 
 
-@pytest.mark.parametrize("n,B,X,stop", [(1000, 65536, -1, 0),      # 2 words per variable
-                                         (1000, 131072, 3, 0),      # 4 words, expurgation
-                                         (1000, 131072, -1, 2000),  # 4 words, exact stop inside a batch
-                                         (6000, 4096, -1, 0),       # 512-thread workgroups
-                                         (64800, 512, 3, 0)])       # byte planes (8 codewords)
-def test_mc_bec_bitsliced_shapes_exact(torch, n, B, X, stop):
+MC_BITS_CASES = [
+    (1000, 65536, -1, 0, "bec_mc_bits_kernel<256,2,u32>"),
+    (1000, 131072, 3, 0, "bec_mc_bits_kernel<256,4,u32>"),      # expurgation
+    (1000, 131072, -1, 2000, "bec_mc_bits_kernel<256,4,u32>"),  # exact stop inside a batch
+    (6000, 4096, -1, 0, "bec_mc_bits_kernel<512,1,u32>"),
+    (64800, 512, 3, 0, "bec_mc_bits_kernel<1024,1,u8>"),
+]
+
+
+@pytest.mark.parametrize("n,B,X,stop,kernel", MC_BITS_CASES, ids=["-".join(map(str, c[:-1])) for c in MC_BITS_CASES])
+def test_mc_bec_bitsliced_shapes_exact(torch, n, B, X, stop, kernel):
     """The bit-sliced BEC Monte-Carlo kernel (32 codewords per word) at every word width and
     workgroup size it uses, against the oracle's message_passing restatement."""
     from iib_project_ldpc_codes_amd.graph import TannerGraph
+    assert bec_plans(n, n // 2, [(BEC_MC, B, 50)])[0]["name"] == kernel
     g = TannerGraph.random_regular(n, 3, 6, seed=23)
     got = _mc_counters(g, "bec", 0.43, 9, B, 50, X=X, stop=stop)
     want = _oracle_bec_counters(g, 0.43, 9, B, 50, X=X, stop=stop)
@@ -504,6 +517,8 @@ def test_mc_bec_bitsliced_shapes_exact(torch, n, B, X, stop):
 
 def _bec_decode_scalar(decoder, g, words, iters, errors=None, chunk=32):
     """Batch decode in chunks of < 64 words: the per-codeword bec_kernel path."""
+    sizes = sorted({min(chunk, len(words) - i) for i in range(0, len(words), chunk)})
+    assert all(p["kernel"] == "Word" for p in bec_plans(g.n, g.m, [(BEC_DECODE, b, iters) for b in sizes]))
     outs = [decoder.bec_decode(g, words[i:i + chunk], iters,
                                errors=None if errors is None else errors[i:i + chunk])
             for i in range(0, len(words), chunk)]
