@@ -63,6 +63,7 @@ SIGNATURES = {
     "ldpc_debug_lane_layout": ([P, P, i, i, i, i, P, P, P, P], i),
     "ldpc_debug_irr_layout": ([P, P, P, P, i, i, P, P, P], i),
     "ldpc_debug_loc_layout": ([P, P, P, P, i, i, i, P, P, P, P], i),
+    "ldpc_debug_loc_chain_layout": ([P, P, P, P, i, i, P, P, P, P, P], i),
     "ldpc_debug_loc_variant": ([P, P, P, P, i, i, i, P], i),
     "ldpc_debug_mc_plan": ([P, i64, i64, i64, i, i, P], i),
     "ldpc_debug_bp_plan": ([P, P, P, P, i, i, i, P, i, P, P], i),

@@ -48,18 +48,21 @@ __device__ __forceinline__ uint32_t bits_parity(const float2 (&x)[D], bool hi, u
     if (j < N) p ^= w(j);
     return p;
 }
-template <int D, int ALGO, bool MIXED = false, bool SGN = false>
+// CL > 0 (the chained layout, bp_loc_kernel): input slot 2 is the thread's chain register *chain,
+// overwritten with that slot's output; the pair's rows hold the other D - 3 inputs.
+template <int D, int ALGO, bool MIXED = false, bool SGN = false, int CL = 0>
 __device__ __forceinline__ int loc_check_pair(float *msg, int W, int Nc, int i, float2 &l0, float2 &l1, float alpha,
-                                              uint32_t lpar = 0u) {
-    constexpr int U = D - 2;
+                                              uint32_t lpar = 0u, float2 *chain = nullptr) {
+    constexpr int C = CL > 0 ? 1 : 0, U = D - 2 - C;
     float2 x[D];
     x[0] = l0;
     x[1] = l1;
+    if constexpr (C) x[2] = *chain;
 #pragma unroll
     for (int r = 0; r < U / 2; ++r) {
         const float4 f = *reinterpret_cast<const float4 *>(msg + W + r * 4 * Nc + 4 * i);
-        x[2 + 2 * r] = make_float2(f.x, f.y);
-        x[3 + 2 * r] = make_float2(f.z, f.w);
+        x[2 + C + 2 * r] = make_float2(f.x, f.y);
+        x[3 + C + 2 * r] = make_float2(f.z, f.w);
     }
     if constexpr (U % 2) x[D - 1] = *reinterpret_cast<const float2 *>(msg + W + (U / 2) * 4 * Nc + 2 * i);
     int unsat = 0;
@@ -96,10 +99,11 @@ __device__ __forceinline__ int loc_check_pair(float *msg, int W, int Nc, int i, 
 #pragma unroll
     for (int r = 0; r < U / 2; ++r)
         *reinterpret_cast<float4 *>(msg + W + r * 4 * Nc + 4 * i) =
-            make_float4(x[2 + 2 * r].x, x[2 + 2 * r].y, x[3 + 2 * r].x, x[3 + 2 * r].y);
+            make_float4(x[2 + C + 2 * r].x, x[2 + C + 2 * r].y, x[3 + C + 2 * r].x, x[3 + C + 2 * r].y);
     if constexpr (U % 2) *reinterpret_cast<float2 *>(msg + W + (U / 2) * 4 * Nc + 2 * i) = x[D - 1];
     l0 = x[0];
     l1 = x[1];
+    if constexpr (C) *chain = x[2];
     return unsat;
 }
 
@@ -169,9 +173,19 @@ __device__ __forceinline__ uint32_t block_count(int pred, uint32_t *flag, int pa
 // VGPRs), so one workgroup's barrier waits overlap the other's work; else one workgroup
 constexpr int loc_waves_per_simd(int T, int KP) { return T == 512 && KP <= 5 ? 4 : 1; }
 
+// CL > 0: the chained layout (loc_layout.cpp) with CL = KP - 1 chain links per thread: threads
+// t < Tq (a.loc_cls_q[1]) own pairs t + k Tq; pair slot k >= 1 takes its input slot 2 from
+// chain[k - 1] and has three LDS inputs (class 1: rows of (KP - 1) Tq pairs from word
+// a.loc_cls_w[1]); var pair 2k + 1, k < CL, has one LDS edge (row 0 of loc_pos) and chain[k].
+// Fixed-count sum-product only.
 template <int DLO, int DHI, int DVN0, int DVN1, int KP, int T, int ALGO, bool ABS0, bool ABS1, bool ET = false,
-          bool MC = false, bool EP = false>
+          bool MC = false, bool EP = false, int CL = 0>
 __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(BpArgs a) {
+    static_assert(CL == 0 || (CL == KP - 1 && ALGO == 0 && !ET && !MC && !EP && DLO == DHI && DVN1 == 2 && !ABS1),
+                  "chained layout: fixed-count sum-product on the one-class shape");
+    // var pair v's last non-local edge is the chain register chain[v / 2]
+    auto chained = [](int v) { return CL > 0 && (v & 1) && (v >> 1) < CL; };
+    float2 chain[CL > 0 ? CL : 1];
     static_assert(!ET || ALGO == 0 || DLO == DHI, "min-sum early stop: one check class");
     static_assert(!ET || 2 * 2 * KP <= 64, "early stop keeps the thread's decisions in one 64-bit word");
     // MSET (min-sum Monte-Carlo with early stop): min-sum messages carry their own signs, so
@@ -216,17 +230,22 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
     const float neutral = SPA ? 1.0f : 0.0f;
 
     // gather the non-local c->v messages of var pair v (slot s) into cv[0 .. DN-1]
+    // (a chained var pair's last edge comes from its chain register)
     auto gather = [&](auto dn_tag, auto abs_tag, int v, const uint32_t (&spv)[DVA], float2 (&cv)[DVA],
                       uint32_t (&a0)[DVA], uint32_t (&a1)[DVA]) {
         constexpr int DN = decltype(dn_tag)::value;
         constexpr bool AB = decltype(abs_tag)::value;
+        const int nl = chained(v) ? DN - 1 : DN;
 #pragma unroll
-        for (int u = 0; u < DN; ++u) {
-            a0[u] = pos_lo_x4(spv[u]);
-            a1[u] = pos_hi_x4(spv[u]);
-        }
+        for (int u = 0; u < DN; ++u)
+            if (u < nl) {
+                a0[u] = pos_lo_x4(spv[u]);
+                a1[u] = pos_hi_x4(spv[u]);
+            }
 #pragma unroll
-        for (int u = 0; u < DN; ++u) cv[u] = make_float2(at(a0[u]), at(a1[u]));
+        for (int u = 0; u < DN; ++u)
+            if (u < nl) cv[u] = make_float2(at(a0[u]), at(a1[u]));
+        if (chained(v)) cv[DN - 1] = chain[v >> 1];
         if constexpr (AB) {
 #pragma unroll
             for (int u = 0; u < DN; ++u) {
@@ -398,7 +417,8 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
 #pragma unroll
             for (int u = 0; u < DVN0; ++u) sp[2 * k][u] = load_sp(2 * k, u);
 #pragma unroll
-            for (int u = 0; u < DVN1; ++u) sp[2 * k + 1][u] = load_sp(2 * k + 1, u);
+            for (int u = 0; u < DVN1; ++u)
+                if (!(chained(2 * k + 1) && u == DVN1 - 1)) sp[2 * k + 1][u] = load_sp(2 * k + 1, u);
         }
         float2 L[VP];  // SPA: E = 2^channel (clamped); min-sum: channel LLR
         if constexpr (MC) {  // (the other decodes: neutral to 0.5 % slower with the batch, registers)
@@ -438,8 +458,12 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             loc[v] = w;
 #pragma unroll
             for (int u = 0; u < DN; ++u) {
-                at(pos_lo_x4(sp[v][u])) = w.x;
-                at(pos_hi_x4(sp[v][u])) = w.y;
+                if (chained(v) && u == DN - 1) {
+                    chain[v >> 1] = w;
+                } else {
+                    at(pos_lo_x4(sp[v][u])) = w.x;
+                    at(pos_hi_x4(sp[v][u])) = w.y;
+                }
             }
         };
         hbits = 0u;
@@ -487,8 +511,12 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
 #pragma unroll
                 for (int j = DV - 1; j >= 1; --j) {
                     const float2 R = sgn(ratio_wire2(j == DV - 1 ? pre[j] : pre[j] * suf));
-                    at(a0[j - 1]) = R.x;
-                    at(a1[j - 1]) = R.y;
+                    if (chained(v) && j == DV - 1) {
+                        chain[v >> 1] = R;
+                    } else {
+                        at(a0[j - 1]) = R.x;
+                        at(a1[j - 1]) = R.y;
+                    }
                     if (j < DV - 1) suf = suf * cv[j - 1];
                 }
                 if (ep && slab_now) slab[v * T + tid] = loc[v] * suf;  // prod of the incoming c->v ratios
@@ -517,7 +545,8 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
 #pragma unroll
                 for (int v = 0; v < VP; ++v)
 #pragma unroll
-                    for (int u = 0; u < DVA; ++u) asm volatile("" : "+v"(sp[v][u]));
+                    for (int u = 0; u < DVA; ++u)
+                        if (!(chained(v) && u == DVA - 1)) asm volatile("" : "+v"(sp[v][u]));
             }
             if constexpr (ALGO == 1) {  // the order masks (ms_sum) are re-derived per iteration, not held
 #pragma unroll
@@ -525,8 +554,26 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             }
             // ---- check phase ----
             if (LDPC_LOC_PRIO) __builtin_amdgcn_s_setprio(0);
+            if constexpr (CL > 0) {
+                // threads t < Tq own all KP pair slots: one branch around the phase
+                const int Tq = a.loc_cls_q[1];
+                if (tid < Tq) {
 #pragma unroll
-            for (int k = 0; k < KP; ++k) {
+                    for (int k = 0; k < KP; ++k) {
+                        int i = tid + (k > 0 ? (k - 1) * Tq : 0);  // index in the pair's class
+                        asm volatile("" : "+v"(i));  // recomputed per iteration, as q below
+                        if (k == 0)
+                            loc_check_pair<DLO, ALGO>(msg, 0, Tq, i, loc[0], loc[1], a.alpha);
+                        else
+                            loc_check_pair<DLO, ALGO, false, false, CL>(msg, a.loc_cls_w[1], (KP - 1) * Tq, i, loc[2 * k],
+                                                                        loc[2 * k + 1], a.alpha, 0u, &chain[k - 1]);
+                        if (LDPC_LOC_CGROUP > 0 && k % LDPC_LOC_CGROUP == LDPC_LOC_CGROUP - 1)
+                            __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < (CL > 0 ? 0 : KP); ++k) {
                 int q = tid + k * T;
                 asm volatile("" : "+v"(q));  // recomputed per iteration: no per-pair addresses held live
                 if (q < a.loc_P) {
@@ -686,7 +733,8 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             uint32_t a0[DVA], a1[DVA], spv[DVA];
             float2 cv[DVA];
 #pragma unroll
-            for (int u = 0; u < DN; ++u) spv[u] = load_sp(v, u);
+            for (int u = 0; u < DN; ++u)
+                if (!(chained(v) && u == DN - 1)) spv[u] = load_sp(v, u);
             gather(dn_tag, abs_tag, v, spv, cv, a0, a1);
             if constexpr (SPA) {
                 float2 s;
@@ -770,6 +818,29 @@ hipError_t launch_loc_deg(const BpPlan &p, const BpArgs &a, int T, int KP, hipSt
 
 template <int ALGO, bool ET, bool MC>
 hipError_t launch_loc_modes(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipStream_t s) {
+    if (p.chain) {  // the chained layout: its tables, two row classes (pair slot 0 | the chained slots)
+        if constexpr (ALGO == 0 && !ET && !MC) {
+            constexpr int KP = kLocChainKP, T = kLocChainT;
+            if (g.chn_Tq <= 0 || g.chn_Tq > T || g.loc_P != KP * g.chn_Tq || !g.chn_var || !g.chn_pos)
+                return hipErrorInvalidValue;
+            a.loc_var = g.chn_var;
+            a.loc_pos = g.chn_pos;
+            a.loc_info = g.chn_info;
+            a.loc_P = g.loc_P;
+            a.loc_ncls = 2;
+            a.loc_words = g.chn_words;
+            a.loc_cls_q[0] = 0; a.loc_cls_q[1] = g.chn_Tq; a.loc_cls_q[2] = g.loc_P;
+            a.loc_cls_w[0] = 0; a.loc_cls_w[1] = 8 * g.chn_Tq; a.loc_cls_w[2] = g.chn_words;
+            a.loc_cls_d[0] = a.loc_cls_d[1] = 6;
+            auto k = bp_loc_kernel<6, 6, 2, 2, KP, T, 0, false, false, false, false, false, kLocChainCL>;
+            const hipError_t e = allow_lds(k, p.lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k, dim3(p.grid), dim3(T), p.lds, s, a);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }
     a.loc_var = g.loc_var;
     a.loc_pos = g.loc_pos;
     a.loc_info = g.loc_info;

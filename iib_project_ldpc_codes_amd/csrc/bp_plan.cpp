@@ -12,6 +12,9 @@
 #ifndef LDPC_LOC
 #define LDPC_LOC 1  // fixed-count decode on bp_loc_kernel when the graph has a local-edge layout
 #endif
+#ifndef LDPC_LOC_CHAIN
+#define LDPC_LOC_CHAIN 1  // fixed-count sum-product decodes on the chained layout where the graph has one
+#endif
 #ifndef LDPC_LOC_MSMC
 #define LDPC_LOC_MSMC 1  // (3,6) min-sum Monte-Carlo (with or without early stop) on bp_loc_kernel
 #endif
@@ -127,6 +130,10 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
             p.threads = g.loc_T;
             const bool mset = et && algo == 1;
             p.lds = loc_lds_bytes(g, iters, mc || mset, mset);
+            // fixed-count sum-product on a graph with a chained layout: its instantiation, its
+            // tables and its (smaller) message LDS; every other mode keeps the plain layout
+            p.chain = LDPC_LOC_CHAIN && g.chn_Tq > 0 && algo == 0 && !et && !mc;
+            if (p.chain) p.lds = pad16((size_t)std::max(g.chn_words + 64, g.n) * 4);
             // early stop with posteriors: persistent workgroups (two per CU, the most any
             // bp_loc_kernel shape keeps resident), each with a slab; early stop without: the same
             // grid on the counter alone

@@ -22,12 +22,15 @@ std::mutex g_mu;  // the drop-in graph cache and the host-buffer entry points (t
 DropInCache g_dropin;
 
 // The layout environment, read here and nowhere else: LDPC_NO_LOC_LAYOUT=1 builds no local-edge
-// layout (tests run the other kernels on the same graphs), LDPC_LOC_T sets its thread count
+// layout (tests run the other kernels on the same graphs), LDPC_NO_LOC_CHAIN=1 no chained layout
+// beside it (fixed-count sum-product decodes then run on the plain one), LDPC_LOC_T sets its thread count
 // (shape experiments); an explicit loc_T (ldpc_debug_loc_variant) goes over the environment's.
 LayoutOptions layout_options(int loc_T = 0) {
     LayoutOptions opt;
     const char *noloc = getenv("LDPC_NO_LOC_LAYOUT");
     opt.loc_layout = !(noloc && noloc[0] == '1');
+    const char *nochain = getenv("LDPC_NO_LOC_CHAIN");
+    opt.loc_chain = !(nochain && nochain[0] == '1');
     if (const char *t = getenv("LDPC_LOC_T")) opt.loc_T = atoi(t);
     if (loc_T) opt.loc_T = loc_T;
     return opt;
@@ -173,6 +176,34 @@ int ldpc_debug_loc_layout(const int32_t *check_ptr, const int32_t *check_var, co
     if (var) std::copy(L.var.begin(), L.var.end(), var);
     if (pos) std::copy(L.pos.begin(), L.pos.end(), pos);
     if (info) std::copy(L.info.begin(), L.info.end(), info);
+    return LDPC_OK;
+}
+
+// The chained layout (build_loc_chain_layout) of the plain T = 512 layout: shape = {Tq, KP, chain
+// links per thread, words, conflicts, T}; var / pos / info as ldpc_debug_loc_layout's, chk
+// [2 KP][T]: the check at pair slot k, half h of thread t (row 2k + h; -1: none).  LDPC_EUNSUP
+// when the graph has no chained layout.
+int ldpc_debug_loc_chain_layout(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                                const int32_t *var_slot, int n, int m, int32_t *shape, int32_t *var, int32_t *pos,
+                                int32_t *info, int32_t *chk) {
+    LDPC_REQUIRE(shape, "null shape");
+    HostGraph h;
+    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
+    LocLayout L;
+    L.T = kLocChainT;
+    LocChainLayout C;
+    if (!h.consistent || !build_loc_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, L) ||
+        !build_loc_chain_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, L, C)) {
+        set_error("no chained layout (needs the (3,6) 512 x 5 local-edge shape, P a multiple of 5, no repeated variable "
+                  "in a check, and a chain cover)");
+        return LDPC_EUNSUP;
+    }
+    shape[0] = C.Tq; shape[1] = kLocChainKP; shape[2] = kLocChainCL; shape[3] = C.words;
+    shape[4] = (int32_t)std::min<long>(C.conflicts, 0x7fffffff); shape[5] = kLocChainT;
+    if (var) std::copy(C.var.begin(), C.var.end(), var);
+    if (pos) std::copy(C.pos.begin(), C.pos.end(), pos);
+    if (info) std::copy(C.info.begin(), C.info.end(), info);
+    if (chk) std::copy(C.chk.begin(), C.chk.end(), chk);
     return LDPC_OK;
 }
 

@@ -22,6 +22,8 @@ hipError_t for_graph_arrays(ldpc_graph &g, const HostGraph &h, const HostLayouts
         {&g.loc_var, &L.loc.var},     {&g.loc_pos, &L.loc.pos},
         {&g.loc_info, &L.loc.info},   {&g.irr_lane, &L.irr_lane},
         {&g.irr_cdeg, &L.irr_cdeg},
+        {&g.chn_var, &L.chain.var},   {&g.chn_pos, &L.chain.pos},
+        {&g.chn_info, &L.chain.info},
     };
     for (const auto &a : arrays) {
         const hipError_t e = f(*a.first, *a.second);

@@ -7,6 +7,9 @@
 #ifndef LDPC_LOC_LAYOUT
 #define LDPC_LOC_LAYOUT 1  // build the local-edge layout (bp_loc_kernel) for rate-1/2 graphs
 #endif
+#ifndef LDPC_LOC_CHAIN
+#define LDPC_LOC_CHAIN 1  // build the chained layout beside it where the shape allows
+#endif
 
 namespace ldpc {
 
@@ -306,6 +309,15 @@ void host_layouts(const HostGraph &h, GraphShape &g, HostLayouts &L, bool layout
         }
         if (built) {
             loc_shape(K, g);
+            // the chained layout beside it (the (3,6) 512 x 5 shape only; a graph without one
+            // keeps the plain layout for every decode)
+            if (LDPC_LOC_CHAIN && opt.loc_chain && loc_variant(g) == kLocReg36 &&
+                build_loc_chain_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, K, L.chain)) {
+                g.chn_Tq = L.chain.Tq;
+                g.chn_words = L.chain.words;
+            } else {
+                L.chain = LocChainLayout();
+            }
         } else {
             K = LocLayout();
         }

@@ -28,11 +28,13 @@ bool build_irr_layout(const HostGraph &h, int &VPT, int &KC, int &DC, int &S, in
 struct HostLayouts {
     std::vector<int32_t> lane_var, lane_slot, irr_lane, irr_cdeg;
     LocLayout loc;
+    LocChainLayout chain;
 };
 
 struct LayoutOptions {
     bool loc_layout = true;  // build the local-edge layout (off: tests run the other kernels on the same graphs)
     int loc_T = 0;           // threads of the local-edge layout, 0 = the shipped choice
+    bool loc_chain = true;   // build the chained layout beside it (off: tests and A/B runs of the plain one)
 };
 
 // Fills g and, with layouts, the kernels' layouts (L and the lane_* / irr_* / loc_* scalars of g).

@@ -32,6 +32,9 @@ struct GraphShape {
     int loc_dvn0 = 0, loc_dvn1 = 0;       // non-local edges per variable, local slot 0 / 1 (max)
     bool loc_abs0 = false, loc_abs1 = false;  // some variable of that slot has fewer
     int loc_cls_q[5] = {0}, loc_cls_d[4] = {0}, loc_cls_w[5] = {0};
+    // Chained local-edge layout beside it (build_loc_chain_layout; fixed-count sum-product
+    // decodes run on it); chn_Tq == 0: none
+    int chn_Tq = 0, chn_words = 0;
 };
 
 // Device-resident Tanner graph: the shape and the device arrays (listed once more, each with the
@@ -54,6 +57,7 @@ struct ldpc_graph : GraphShape {
     int32_t *loc_pos = nullptr;   // [2*KP][DVN][T] non-local edge u's LDS words, h=0 | h=1 << 16
     int32_t *loc_info = nullptr;  // [2*KP][T] bit u + 4h: edge u present; bits 8+2h: local edge index jl;
                                   // bit 16 + 4h + jl: the same one-hot (min-sum order masks)
+    int32_t *chn_var = nullptr, *chn_pos = nullptr, *chn_info = nullptr;  // the chained layout's, same formats
 };
 
 // Local-edge layout (loc_layout.cpp): see the comment there.
@@ -68,6 +72,23 @@ struct LocLayout {
 };
 bool build_loc_layout(int n, int m, const std::vector<int32_t> &cptr, const std::vector<int32_t> &cvar,
                       const std::vector<int32_t> &vptr, const std::vector<int32_t> &vslot, LocLayout &L);
+
+// Chained local-edge layout (loc_layout.cpp, "Chained layout"): the (3,6) T = 512, KP = 5 shape
+// with the five .x (and the five .y) checks of a thread on a path whose links are the checks'
+// slot-1 local variables, so the edge from each link variable to the next check of the path stays
+// in a VGPR too.  Built beside the plain layout; Tq == 0: none.
+constexpr int kLocChainT = 512, kLocChainKP = 5, kLocChainCL = kLocChainKP - 1;
+struct LocChainLayout {
+    int Tq = 0;          // threads that own check pairs: pair q = t + k Tq (t < Tq, k < KP)
+    int words = 0;       // LDS message words (32 Tq)
+    long conflicts = 0;  // as LocLayout::conflicts
+    // var, pos, info: LocLayout's formats at T = 512 (var pairs 2k + 1, k < KP - 1: one LDS edge,
+    // row 0 of pos); chk[(2k + h) T + t]: the check at pair slot k, half h of thread t (-1: none)
+    std::vector<int32_t> var, pos, info, chk;
+};
+bool build_loc_chain_layout(int n, int m, const std::vector<int32_t> &cptr, const std::vector<int32_t> &cvar,
+                            const std::vector<int32_t> &vptr, const std::vector<int32_t> &vslot, const LocLayout &plain,
+                            LocChainLayout &C);
 
 // Check-degree range of a layout's classes (a mixed class counts its smaller check); false
 // when a mixed class is not (dhi - 1, dhi) -- the kernel pads a mixed pair's smaller check by
@@ -222,6 +243,7 @@ struct BpPlan {
     int threads = 0, grid = 0;
     size_t lds = 0;             // dynamic LDS bytes
     int lds_slots = 0;          // bp_generic_kernel / bp_ens_kernel <*,gmem>: message slots [0, lds_slots) kept in LDS
+    bool chain = false;         // bp_loc_kernel: the chained layout's instantiation and tables
     bool persistent = false;    // bp_loc_kernel: the grid pulls codewords from a counter in scratch
     size_t slab = 0;            // bytes of per-workgroup slabs at the start of scratch (0: none)
     long counter = -1;          // byte offset of the work counter in scratch (-1: none)

@@ -453,3 +453,266 @@ bool build_loc_layout(int n, int m, const std::vector<int32_t> &cptr, const std:
         }
     return L.words + 64 < 65536;
 }
+
+// ---------------------------------------------------------------------------
+// Chained layout.  On top of the one local edge per variable, the five .x checks of a thread
+// (pair slots k = 0 .. 4) form a path c_0 - c_1 - ... - c_4 in which c_k and c_{k+1} share a
+// variable w_k, and w_k is the slot-1 local variable of c_k; the same for the five .y checks.
+// The edge w_k -> c_{k+1} then has both ends in one thread and stays in a VGPR (the kernel's
+// chain[k]) as the local edge does: input slot 2 of check pair k + 1, one of the two non-local
+// edges of var pair 2k + 1.  Per thread 8 of the 40 messages leave LDS.
+//
+// Threads t < Tq = P / KP own pairs q = t + k Tq.  LDS rows in two classes:
+//   k = 0:  Tq pairs, 4 LDS inputs (two float4 rows):          (u/2)*4*Tq + 4t + 2(u%2) + h
+//   k >= 1: 4 Tq pairs, i = q - Tq, 3 LDS inputs (float4 row + float2 row) from word 8 Tq:
+//           8 Tq + 4i + 2u + h (u < 2),  8 Tq + 16 Tq + 2i + h (u = 2)
+// words = 32 Tq.  var / pos / info as the plain layout's at T = 512 (threads >= Tq: no variables,
+// dummy words); a chained var pair's one LDS edge is row 0 of pos.
+//
+// Construction (deterministic, fixed seed; any failure: no chained layout): checks are the
+// nodes of a graph, adjacent when they share a variable.  A Hamiltonian path over them by Posa
+// rotation-extension, a step refused when (a) the two links at a node would be the same
+// variable or (b) some check would have more than 2 of its variables serving as the link of two
+// other consecutive checks (without the quota a few checks per graph end with every spare
+// variable taken as someone else's link, and the matching below is short by that many).  The
+// path is cut into groups of KP; groups 2t, 2t + 1 are thread t's .x and .y paths.  One
+// bipartite matching then gives every variable its role: slot 0 of a check (any of its
+// variables), slot 1 (a variable shared with the next check of the group; the group's last
+// check: any).
+// ---------------------------------------------------------------------------
+bool build_loc_chain_layout(int n, int m, const std::vector<int32_t> &cptr, const std::vector<int32_t> &cvar,
+                            const std::vector<int32_t> &vptr, const std::vector<int32_t> &vslot, const LocLayout &plain,
+                            LocChainLayout &C) {
+    C = LocChainLayout();
+    constexpr int KP = kLocChainKP, T = kLocChainT, D = 6, DV = 3, DVN = 2;
+    if (plain.T != T || plain.KP != KP || plain.ncls != 1 || plain.cls_d[0] != D || plain.DVN != DVN ||
+        plain.DVN0 != DVN || plain.DVN1 != DVN || plain.ABS0 || plain.ABS1)
+        return false;
+    const int P = plain.P;
+    if (2 * P != m || n != 2 * m || P % KP || P / KP > T) return false;
+    const int Tq = P / KP;
+    for (int c = 0; c < m; ++c) {
+        if (cptr[c + 1] - cptr[c] != D) return false;
+        for (int e = cptr[c]; e < cptr[c + 1]; ++e)
+            for (int f = cptr[c]; f < e; ++f)
+                if (cvar[e] == cvar[f]) return false;  // a check holds a variable twice
+    }
+    std::vector<int> slot_check(cvar.size());
+    for (int c = 0; c < m; ++c)
+        for (int e = cptr[c]; e < cptr[c + 1]; ++e) slot_check[e] = c;
+    std::vector<int> vc((size_t)n * DV);  // the checks of each variable, variable_to_check_list order
+    for (int v = 0; v < n; ++v) {
+        if (vptr[v + 1] - vptr[v] != DV) return false;
+        for (int j = 0; j < DV; ++j) vc[(size_t)v * DV + j] = slot_check[vslot[vptr[v] + j]];
+    }
+    auto third = [&](int v, int a, int b) {
+        for (int j = 0; j < DV; ++j)
+            if (vc[(size_t)v * DV + j] != a && vc[(size_t)v * DV + j] != b) return vc[(size_t)v * DV + j];
+        return -1;
+    };
+    // ---- Hamiltonian path ----
+    std::vector<int> path, at_pos(m, -1), link(m, -1), foreign(m, 0);  // link[i]: between path[i], path[i + 1]
+    path.reserve(m);
+    path.push_back(0);
+    at_pos[0] = 0;
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
+    const long cap = 64L * m;
+    int stuck = 0;
+    for (long steps = 0; (int)path.size() < m; ++steps) {
+        if (steps > cap) return false;
+        const int k = (int)path.size() - 1, e = path[k];
+        int ext[D * (DV - 1)][2], next = 0, rot[D * (DV - 1)][2], nrot = 0;
+        for (int s = cptr[e]; s < cptr[e + 1]; ++s) {
+            const int w = cvar[s];
+            if (k > 0 && w == link[k - 1]) continue;  // (a) at e
+            for (int j = 0; j < DV; ++j) {
+                const int y = vc[(size_t)w * DV + j];
+                if (y == e) continue;
+                const int z = third(w, e, y), i = at_pos[y];
+                if (i < 0) {
+                    if (foreign[z] >= 2) continue;  // (b)
+                    ext[next][0] = y;
+                    ext[next++][1] = w;
+                } else {
+                    if (i == k - 1 || (i > 0 && link[i - 1] == w)) continue;  // the predecessor; (a) at y
+                    const int zr = third(link[i], path[i], path[i + 1]);  // the link the rotation removes
+                    if (foreign[z] - (zr == z ? 1 : 0) >= 2) continue;    // (b)
+                    rot[nrot][0] = y;
+                    rot[nrot++][1] = w;
+                }
+            }
+        }
+        if (next) {
+            const int pick = (int)(rnd() % (uint64_t)next), y = ext[pick][0], w = ext[pick][1];
+            link[k] = w;
+            ++foreign[third(w, e, y)];
+            at_pos[y] = k + 1;
+            path.push_back(y);
+            stuck = 0;
+        } else if (nrot) {
+            const int pick = (int)(rnd() % (uint64_t)nrot), y = rot[pick][0], w = rot[pick][1], i = at_pos[y];
+            --foreign[third(link[i], path[i], path[i + 1])];
+            ++foreign[third(w, e, y)];
+            std::reverse(path.begin() + i + 1, path.end());
+            std::reverse(link.begin() + i + 1, link.begin() + k);
+            link[i] = w;
+            for (int j = i + 1; j <= k; ++j) at_pos[path[j]] = j;
+            stuck = 0;
+        } else {  // no admissible step from this end: go on from the other one
+            if (++stuck > 2) return false;
+            std::reverse(path.begin(), path.end());
+            std::reverse(link.begin(), link.begin() + k);
+            for (int j = 0; j <= k; ++j) at_pos[path[j]] = j;
+        }
+    }
+    // ---- groups and roles ----
+    // group g = path[KP g .. KP g + KP - 1]: thread g / 2, half g % 2, pair slot = index in the group
+    std::vector<int> nxt(m, -1), prv(m, -1);  // the next / previous check of the group
+    for (int p = 0; p < m; ++p) {
+        if (p % KP != KP - 1) nxt[path[p]] = path[p + 1];
+        if (p % KP != 0) prv[path[p]] = path[p - 1];
+    }
+    auto holds = [&](int c, int v) {
+        for (int e = cptr[c]; e < cptr[c + 1]; ++e)
+            if (cvar[e] == v) return true;
+        return false;
+    };
+    std::vector<std::vector<int>> adj(2 * (size_t)m);  // role 2c + s -> candidate variables
+    for (int c = 0; c < m; ++c)
+        for (int e = cptr[c]; e < cptr[c + 1]; ++e) {
+            adj[2 * (size_t)c].push_back(cvar[e]);
+            if (nxt[c] < 0 || holds(nxt[c], cvar[e])) adj[2 * (size_t)c + 1].push_back(cvar[e]);
+        }
+    std::vector<int> role_var;
+    if (!assign(adj, std::vector<int>(n, 1), n, role_var)) return false;
+    std::vector<int> role_of(n, -1);
+    for (int r = 0; r < 2 * m; ++r) {
+        if (role_var[r] < 0 || role_of[role_var[r]] >= 0) return false;
+        role_of[role_var[r]] = r;
+    }
+    // ---- LDS words ----
+    // edge e of check c: local (the two role variables), chain (the previous check's slot-1
+    // variable) or LDS input urow[e] = 0 .. U - 1 of c
+    C.Tq = Tq;
+    C.words = 32 * Tq;
+    std::vector<int> kof(m), tof(m), hof(m);
+    for (int p = 0; p < m; ++p) {
+        const int c = path[p], g = p / KP;
+        kof[c] = p % KP;
+        tof[c] = g / 2;
+        hof[c] = g % 2;
+    }
+    const size_t E = cvar.size();
+    std::vector<int> urow(E, -1);
+    std::vector<std::vector<int>> nl(m);  // LDS edges of each check
+    for (int c = 0; c < m; ++c) {
+        const int U = kof[c] == 0 ? 4 : 3;
+        int u = 0, loc = 0, ch = 0;
+        for (int e = cptr[c]; e < cptr[c + 1]; ++e) {
+            const int v = cvar[e];
+            if (role_of[v] >> 1 == c) { ++loc; continue; }
+            if (prv[c] >= 0 && role_of[v] == 2 * prv[c] + 1) { ++ch; continue; }
+            if (u == U) return false;
+            urow[e] = u++;
+            nl[c].push_back(e);
+        }
+        if (loc != 2 || u != U || ch != (kof[c] ? 1 : 0)) return false;
+    }
+    auto wordf = [&](int e) {
+        const int c = slot_check[e], k = kof[c], t = tof[c], h = hof[c], u = urow[e];
+        if (k == 0) return (u / 2) * 4 * Tq + 4 * t + 2 * (u % 2) + h;
+        const int i = t + (k - 1) * Tq;
+        return u < 2 ? 8 * Tq + 4 * i + 2 * u + h : 8 * Tq + 16 * Tq + 2 * i + h;
+    };
+    // ---- bank-conflict pass: row swaps among a check's LDS inputs (the chain-preserving move
+    // that leaves every gather's cell where it is) ----
+    // cell of an LDS edge: (var pair of its variable, its index among the variable's LDS
+    // edges, half, half wave)
+    const int G = T / 32, VP = 2 * KP;
+    std::vector<int> vu(E, -1), cell(E, -1), cw(E, -1);
+    for (int v = 0; v < n; ++v) {
+        int u = 0;
+        for (int j = 0; j < DV; ++j) {
+            const int e = vslot[vptr[v] + j];
+            if (urow[e] >= 0) vu[e] = u++;
+        }
+        const int r = role_of[v], c = r >> 1, s = r & 1;
+        if (u != (s == 1 && nxt[c] >= 0 ? 1 : 2)) return false;
+        for (int j = 0; j < DV; ++j) {
+            const int e = vslot[vptr[v] + j];
+            if (urow[e] >= 0) cell[e] = (((2 * kof[c] + s) * DVN + vu[e]) * 2 + hof[c]) * G + tof[c] / 32;
+        }
+    }
+    const size_t ncell = (size_t)VP * DVN * 2 * G;
+    std::vector<int> cnt(ncell * 32, 0);
+    for (size_t e = 0; e < E; ++e)
+        if (urow[e] >= 0) {
+            cw[e] = wordf((int)e);
+            ++cnt[(size_t)cell[e] * 32 + (cw[e] & 31)];
+        }
+    auto cost = [&](int cl) {
+        int mx = 0, ex = 0;
+        for (int b = 0; b < 32; ++b) {
+            const int c = cnt[(size_t)cl * 32 + b];
+            mx = std::max(mx, c);
+            ex += c > 1 ? c - 1 : 0;
+        }
+        return (mx > 0 ? mx - 1 : 0) * 8 + ex;
+    };
+    long moves = (long)E * LDPC_LOC_SEARCH;
+    if (const char *ev = getenv("LDPC_LOC_SEARCH")) moves = (long)E * atol(ev);  // experiments
+    for (long it = 0; it < moves; ++it) {
+        const int c = (int)(rnd() % (uint64_t)m), U = (int)nl[c].size();
+        const int ea = nl[c][rnd() % U], eb = nl[c][rnd() % U];
+        if (ea == eb) continue;
+        const int before = cost(cell[ea]) + (cell[eb] != cell[ea] ? cost(cell[eb]) : 0);
+        auto move = [&]() {
+            --cnt[(size_t)cell[ea] * 32 + (cw[ea] & 31)];
+            --cnt[(size_t)cell[eb] * 32 + (cw[eb] & 31)];
+            std::swap(urow[ea], urow[eb]);
+            cw[ea] = wordf(ea);
+            cw[eb] = wordf(eb);
+            ++cnt[(size_t)cell[ea] * 32 + (cw[ea] & 31)];
+            ++cnt[(size_t)cell[eb] * 32 + (cw[eb] & 31)];
+        };
+        move();
+        const int after = cost(cell[ea]) + (cell[eb] != cell[ea] ? cost(cell[eb]) : 0);
+        if (after > before) move();  // every move is its own inverse
+    }
+    for (size_t cl = 0; cl < ncell; ++cl) {
+        int mx = 0;
+        for (int b = 0; b < 32; ++b) mx = std::max(mx, cnt[cl * 32 + b]);
+        C.conflicts += mx > 0 ? mx - 1 : 0;
+    }
+    // ---- thread layout ----
+    C.var.assign((size_t)VP * 2 * T, -1);
+    C.pos.assign((size_t)VP * DVN * T, 0);
+    C.info.assign((size_t)VP * T, 0);
+    C.chk.assign((size_t)KP * 2 * T, -1);
+    const int dummy = C.words;  // + (t & 63): threads without variables, the unused row of a chained var pair
+    for (int t = 0; t < T; ++t)
+        for (int vi = 0; vi < VP; ++vi)
+            for (int u = 0; u < DVN; ++u)
+                C.pos[((size_t)vi * DVN + u) * T + t] = (int32_t)((uint32_t)(dummy + (t & 63)) * 0x10001u);
+    for (int c = 0; c < m; ++c) C.chk[((size_t)kof[c] * 2 + hof[c]) * T + tof[c]] = c;
+    for (int v = 0; v < n; ++v) {
+        const int r = role_of[v], c = r >> 1, s = r & 1, t = tof[c], h = hof[c], vi = 2 * kof[c] + s;
+        C.var[((size_t)vi * 2 + h) * T + t] = v;
+        uint32_t info = 0;
+        int u = 0, jl = 0;
+        for (int j = 0; j < DV; ++j) {
+            const int e = vslot[vptr[v] + j];
+            if (slot_check[e] == c) { jl = j; continue; }
+            if (urow[e] < 0) continue;  // the chain edge
+            int32_t &pk = C.pos[((size_t)vi * DVN + u) * T + t];
+            pk = (int32_t)(((uint32_t)pk & ~(0xFFFFu << (16 * h))) | ((uint32_t)cw[e] << (16 * h)));
+            info |= 1u << (u + 4 * h);
+            ++u;
+        }
+        info |= (uint32_t)jl << (8 + 2 * h);
+        info |= 1u << (16 + 4 * h + jl);
+        C.info[(size_t)vi * T + t] |= (int32_t)info;
+    }
+    return true;
+}

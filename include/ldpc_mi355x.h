@@ -352,6 +352,19 @@ int ldpc_debug_loc_layout(const int32_t *check_ptr, const int32_t *check_var, co
                           int32_t *info);
 
 /*
+ * The chained local-edge layout that fixed-count sum-product decodes of (3,6) codes run on (host
+ * only): the plain T = 512 layout with each thread's five .x (and five .y) checks on a path
+ * whose link variables keep a second edge in registers (csrc/loc_layout.cpp).  shape: int32[6] =
+ * {Tq, KP, chain links per thread, words, bank-conflict cost, T}; var, pos, info: as
+ * ldpc_debug_loc_layout's at T = 512 with DVN = 2; chk: int32[2*KP*T], the check at pair slot k,
+ * half h of thread t at (2k + h)*T + t (-1: none).  NULL arrays: shape only.  Returns
+ * LDPC_EUNSUP when the graph has no chained layout.
+ */
+int ldpc_debug_loc_chain_layout(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                                const int32_t *var_slot, int n, int m, int32_t *shape, int32_t *var, int32_t *pos,
+                                int32_t *info, int32_t *chk);
+
+/*
  * Host-only: the launch plans of `count` soft-decoding calls on one CSR graph (csrc/bp_plan.cpp
  * bp_plan), from the host layouts alone; cus: compute units of the device planned for.
  * calls[i] = {B, iters, algo, early_stop, mc, want_post}; out[i] int64[9] = {path, threads,

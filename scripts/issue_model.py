@@ -57,22 +57,25 @@ LDS_CYC = {"ds_read_b128": 4, "ds_write_b128": 13, "ds_read_b32": 2, "ds_write_b
 # it undercounts the packed ops' measured cost; both are reported.
 VALU_CYC = {"packed": 5.3, "plain": 4.2, "trans": 8.2}
 KERNELS = {
-    "loc": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb0ELb0ELb0EEEvNS0_6BpArgsE",
+    "loc": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb0ELb0ELb0ELi0EEEvNS",
             "bp_loc_kernel<6,6,2,2,KP=5,T=512,SPA,fixed-count>", 512, 5),
-    "loc1024": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi3ELi1024ELi0ELb0ELb0ELb0ELb0ELb0EEEvNS0_6BpArgsE",
+    # the chained layout (csrc/loc_layout.cpp): CL = 4 chain links per thread
+    "loc_chain": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb0ELb0ELb0ELi4EEEvNS",
+                  "bp_loc_kernel<6,6,2,2,KP=5,T=512,SPA,fixed-count,CL=4>", 512, 5),
+    "loc1024": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi3ELi1024ELi0ELb0ELb0ELb0ELb0ELb0ELi0EEEvNS",
                 "bp_loc_kernel<6,6,2,2,KP=3,T=1024,SPA,fixed-count>", 1024, 3),
-    "loc_et": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb1ELb0ELb0EEEvNS0_6BpArgsE",
+    "loc_et": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb1ELb0ELb0ELi0EEEvNS",
                "bp_loc_kernel<6,6,2,2,KP=5,T=512,SPA,early-stop>", 512, 5),
-    "loc_ep": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb1ELb0ELb1EEEvNS0_6BpArgsE",
+    "loc_ep": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb1ELb0ELb1ELi0EEEvNS",
                "bp_loc_kernel<6,6,2,2,KP=5,T=512,SPA,early-stop+posteriors>", 512, 5),
-    "loc_ms": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi1ELb0ELb0ELb0ELb0ELb0EEEvNS0_6BpArgsE",
+    "loc_ms": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi1ELb0ELb0ELb0ELb0ELb0ELi0EEEvNS",
                "bp_loc_kernel<6,6,2,2,KP=5,T=512,min-sum,fixed-count>", 512, 5),
-    "lds36": ("_ZN4ldpc12_GLOBAL__N_113bp_lds_kernelILi3ELi6ELi1024ELi10ELi0ELb0ELb0EEEvNS0_6BpArgsE",
+    "lds36": ("_ZN4ldpc12_GLOBAL__N_113bp_lds_kernelILi3ELi6ELi1024ELi10ELi0ELb0ELb0EEEvNS",
               "bp_lds_kernel<3,6,1024,10,SPA,fixed-count>", 1024, None),
 }
 
 
-def loc_parts(bb, T, KP, stats=None):
+def loc_parts(bb, T, KP, stats=None, CL=0):
     """stats (scripts/diag/decode_launch.py output): early-stop launches -- per codeword-iteration
     the check blocks run check_phases / sum_its times, the variable block variable_phases /
     sum_its, the per-codeword blocks batch / sum_its (fixed count: 1, (ITERS-1)/ITERS, 1/ITERS)."""
@@ -89,6 +92,16 @@ def loc_parts(bb, T, KP, stats=None):
     # (round 5: the one-class check phase has no per-pair branch -- one block holding all KP
     # pairs' 2 * KP ds_write_b128, run by every wave)
     chk = [i for i, (_, ins) in enumerate(bb) if ins.count("ds_write_b128") == 2]
+    if CL:
+        # the chained layout: pair slot 0 as before; slots 1 .. CL write one float4 row and one float2
+        # row (three LDS inputs, the fourth is the chain register); threads t < Tq = P / KP own all
+        # KP slots, so every check block runs in ceil(Tq / 64) waves; the variable phase gathers and
+        # scatters 8 KP - 2 CL words
+        chk += [i for i, (_, ins) in enumerate(bb) if ins.count("ds_write_b128") == 1 and ins.count("ds_write_b64") == 1]
+        chk.sort()
+        if len(chk) != KP:  # one branch around the phase: a single block holds every slot's row writes
+            chk = [i for i, (_, ins) in enumerate(bb)
+                   if ins.count("ds_write_b128") == 2 * KP - CL and ins.count("ds_write_b64") == CL]
     one = [i for i, (_, ins) in enumerate(bb) if ins.count("ds_write_b128") == 2 * KP]
     if len(one) == 1 and len(chk) != KP:
         chk = one
@@ -103,12 +116,12 @@ def loc_parts(bb, T, KP, stats=None):
         if ins.count("ds_read_b32") >= 4 and ins.count("ds_write_b32") >= 4:
             var.append(i)
             nr += ins.count("ds_read_b32")
-            if nr >= 8 * KP:
+            if nr >= 8 * KP - 2 * CL:
                 break
-    assert nr == 8 * KP and sum(bb[i][1].count("ds_write_b32") for i in var) == 8 * KP, (var, nr)
+    assert nr == 8 * KP - 2 * CL and sum(bb[i][1].count("ds_write_b32") for i in var) == 8 * KP - 2 * CL, (var, nr)
     execs = {}
     for k, i in enumerate(chk):
-        lanes = min(max(P - k * T, 0), T) if len(chk) == KP else T
+        lanes = P // KP if CL else (min(max(P - k * T, 0), T) if len(chk) == KP else T)
         execs[i] = (lanes + 63) // 64 * r_chk
     for i in var:
         execs[i] = waves * r_var
@@ -148,10 +161,11 @@ def main():
     sha = argv[3] if len(argv) > 3 else None
     sym, label, T, KP = KERNELS[kind]
     lines = open(src).read().split("\n")
-    a = next(k for k, l in enumerate(lines) if l.startswith(sym + ":"))
+    a = next(k for k, l in enumerate(lines) if l.startswith(sym) and l.split(";")[0].rstrip().endswith(":"))
     b = next(k for k in range(a, len(lines)) if "s_endpgm" in lines[k])
     bb = blocks(lines[a:b])
-    parts, wx = loc_parts(bb, T, KP, stats) if kind.startswith("loc") else lds36_parts(bb, T)
+    parts, wx = (loc_parts(bb, T, KP, stats, CL=4 if kind == "loc_chain" else 0) if kind.startswith("loc")
+                 else lds36_parts(bb, T))
     valu = collections.Counter()
     lds = collections.Counter()
     for ins, k in parts:
