@@ -83,4 +83,58 @@ hipError_t launch_mc_decode(const ldpc_graph &g, int channel, float p, float p2,
     return launch_bp(g, a, d_scratch, scratch_bytes, algo, early_stop != 0, true, stream);
 }
 
+// ---- the layered schedule: one bp_layer_plan per call, bp_layer.hip launches from it
+namespace {
+
+hipError_t launch_layered(const ldpc_graph &g, LayerArgs a, float *d_scratch, size_t scratch_bytes, int algo, bool et,
+                          bool mc, hipStream_t s) {
+    const BpPlan p = bp_layer_plan(g, a.B, a.max_iters, algo, et, mc, a.post != nullptr, device_cus());
+    if (p.path == BpPath::None || !g.lay_tab || !g.lay_var) return hipErrorNotSupported;
+    if (p.scratch > (d_scratch ? scratch_bytes : 0)) return hipErrorInvalidValue;  // as launch_bp
+    a.tab = g.lay_tab;
+    a.var = g.lay_var;
+    a.n = g.n;
+    a.m = g.m;
+    a.E = g.E;
+    a.L = g.lay_L;
+    a.scratch = d_scratch;
+    return launch_layer(p, a, algo, et, mc, s);
+}
+
+}  // namespace
+
+size_t layer_scratch_bytes(const ldpc_graph &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post) {
+    return bp_layer_plan(g, B, iters, algo, early_stop, mc, want_post, device_cus()).scratch;
+}
+
+hipError_t launch_layer_decode(const ldpc_graph &g, const float *d_llr, int B, int max_iters, int algo, float alpha,
+                               int early_stop, float *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream,
+                               float *d_scratch, size_t scratch_bytes) {
+    if (B <= 0) return hipSuccess;
+    LayerArgs a{};
+    a.B = B;
+    a.max_iters = max_iters;
+    a.alpha = alpha;
+    a.llr = d_llr;
+    a.post = d_post;
+    a.hard = d_hard;
+    a.its = d_its;
+    return launch_layered(g, a, d_scratch, scratch_bytes, algo, early_stop != 0, false, stream);
+}
+
+hipError_t launch_mc_layer(const ldpc_graph &g, int channel, float p, float p2, uint64_t seed, uint64_t first_cw,
+                           int B, int max_iters, int algo, float alpha, int early_stop, int32_t *trial,
+                           int32_t *trial_its, hipStream_t stream, float *d_scratch, size_t scratch_bytes) {
+    if (B <= 0) return hipSuccess;
+    LayerArgs a{};
+    a.B = B;
+    a.max_iters = max_iters;
+    a.alpha = alpha;
+    a.ch = make_chan(channel, p, p2, seed);
+    a.first_cw = first_cw;
+    a.trial = trial;
+    a.its = trial_its;
+    return launch_layered(g, a, d_scratch, scratch_bytes, algo, early_stop != 0, true, stream);
+}
+
 }  // namespace ldpc

@@ -226,4 +226,39 @@ BpPlan bp_ens_plan(int n, int dv, int dc, int B, int iters, int /*algo*/, bool /
     return p;
 }
 
+// bp_layer_kernel: the graph's layer schedule and its size decide.  algo, early stop and
+// want_post select the instantiation, not the layout.
+BpPlan bp_layer_plan(const GraphShape &g, int B, int iters, int /*algo*/, bool /*early_stop*/, bool mc,
+                     bool /*want_post*/, int cus) {
+    BpPlan p;
+    if (!g.consistent || g.lay_L <= 0 || g.max_cdeg > kLayerMaxD) return p;
+    const size_t words = (size_t)g.n + (size_t)g.E, fixed = mc ? curve_bytes(iters) : 0;
+    if (fixed > kLdsMax - 4096) return p;  // no room for the curve alone: no kernel
+    const int w = g.max_cdeg <= 8 ? 0 : (g.max_cdeg <= 16 ? 1 : 2);
+    static const BpPath paths[2][3] = {{BpPath::LayerG8, BpPath::LayerG16, BpPath::LayerG32},
+                                       {BpPath::Layer8, BpPath::Layer16, BpPath::Layer32}};
+    static const char *const names[2][3] = {
+        {"bp_layer_kernel<8,gmem>", "bp_layer_kernel<16,gmem>", "bp_layer_kernel<32,gmem>"},
+        {"bp_layer_kernel<8,lds>", "bp_layer_kernel<16,lds>", "bp_layer_kernel<32,lds>"}};
+    // one budget for both forms (gmem_plan's): the block is wholly in LDS exactly when the slab
+    // form would keep every word of it there
+    const bool lds = fixed + words * 4 <= kLdsMax - 4096;
+    size_t slab_per_wg = 0;
+    if (lds) {
+        p.threads = 256;
+        p.grid = B;
+        p.lds = fixed + words * 4;
+    } else {
+        // one workgroup per CU striding over the batch: the slabs stay as few as run at once
+        p.grid = std::min(B, std::min(cus, LDPC_GMEM_GRID));
+        gmem_plan(p, fixed, words);
+        slab_per_wg = layer_block_bytes((size_t)g.n, (size_t)g.E);
+    }
+    p.path = paths[lds][w];
+    p.name = names[lds][w];
+    p.slab = slab_per_wg * (size_t)p.grid;
+    p.scratch = p.slab;
+    return p;
+}
+
 }  // namespace ldpc

@@ -452,6 +452,100 @@ int ldpc_mc_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t se
     return LDPC_OK;
 }
 
+// --------------------------- layered schedule ------------------------------
+static const char *const kNoSchedule =
+    "graph has no layer schedule (needs consistent lists, check degrees 1..32, no check holding a variable twice)";
+
+// The argument checks the two layered entries share; LDPC_EUNSUP for a graph without a schedule
+static int layered_check(const ldpc_graph *g, int algo) {
+    LDPC_REQUIRE(algo == LDPC_ALGO_SPA || algo == LDPC_ALGO_MINSUM, "algo must be LDPC_ALGO_SPA or LDPC_ALGO_MINSUM");
+    LDPC_REQUIRE(g->consistent,
+                 "soft decoding needs consistent edge lists (each (v,c) pair listed equally often on both sides)");
+    if (g->lay_L <= 0) {
+        set_error(kNoSchedule);
+        return LDPC_EUNSUP;
+    }
+    return LDPC_OK;
+}
+
+int ldpc_bp_layered_decode_batch_dev(const ldpc_graph *g, const float *d_llr, int B, int max_iters, int algo,
+                                     float alpha, int early_stop, float *d_post, uint8_t *d_hard, int32_t *d_its,
+                                     void *stream) {
+    LDPC_REQUIRE(g && (B == 0 || d_llr) && B >= 0 && max_iters >= 0, "bad soft batch arguments");
+    LDPC_TRY(layered_check(g, algo));
+    if (B == 0) return LDPC_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    Workspace &ws = workspace(stream);
+    std::lock_guard<std::mutex> wl(ws.mu);
+    const size_t sb = layer_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, false, d_post != nullptr);
+    float *scratch;
+    LDPC_ALLOCATED(get_scratch(ws, sb, scratch));
+    LDPC_HIP(launch_layer_decode(*g, d_llr, B, max_iters, algo, alpha, early_stop, d_post, d_hard, d_its,
+                                 static_cast<hipStream_t>(stream), scratch, sb ? ws.scratch.cap : 0));
+    return LDPC_OK;
+}
+
+int ldpc_mc_layered_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t seed, uint64_t first_cw, int B,
+                              int max_iters, int algo, float alpha, int early_stop, int expurgation,
+                              int64_t stop_frame_errors, int64_t *d_counters, void *stream) {
+    LDPC_REQUIRE(g && d_counters && B >= 0 && max_iters >= 0, "bad MC arguments");
+    LDPC_REQUIRE(channel != LDPC_CH_BEC, "the layered schedule decodes the BSC and the BI-AWGN channel (BEC: ldpc_mc_batch_dev)");
+    float p, p2;
+    LDPC_TRY(channel_params(channel, param, &p, &p2));
+    LDPC_TRY(layered_check(g, algo));
+    if (B == 0) return LDPC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only: devices launch in parallel
+    std::lock_guard<std::mutex> wl(ws.mu);
+    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
+    int32_t *cut = ws.cutoff.get<int32_t>(4);
+    const size_t sb = layer_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, true, false);
+    float *scratch;
+    LDPC_ALLOCATED(trial && its && cut && get_scratch(ws, sb, scratch));
+    LDPC_HIP(launch_mc_layer(*g, channel, p, p2, seed, first_cw, B, max_iters, algo, alpha, early_stop, trial, its, s,
+                             scratch, sb ? ws.scratch.cap : 0));
+    LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
+    return LDPC_OK;
+}
+
+const char *ldpc_layer_rule(void) { return kLayerRule; }
+
+int ldpc_debug_layer_schedule(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                              const int32_t *var_slot, int n, int m, int32_t *num_layers, int32_t *layer) {
+    LDPC_REQUIRE(num_layers, "null num_layers");
+    HostGraph h;
+    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
+    LayerSchedule S;
+    if (!build_layer_schedule(h, S)) {
+        set_error(kNoSchedule);
+        return LDPC_EUNSUP;
+    }
+    *num_layers = S.L;
+    if (layer) std::copy(S.layer.begin(), S.layer.end(), layer);
+    return LDPC_OK;
+}
+
+int ldpc_debug_layer_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                          const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
+                          char *names) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
+    HostGraph h;
+    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
+    GraphShape g;
+    HostLayouts L;
+    host_layouts(h, g, L, true, layout_options());
+    if (g.lay_L <= 0) {
+        set_error(kNoSchedule);
+        return LDPC_EUNSUP;
+    }
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 6 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        write_plan(bp_layer_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus), i, out, names);
+    }
+    return LDPC_OK;
+}
+
 // --------------------------- random graphs / ensemble MC -------------------
 static int check_regular_shape(int n, int dv, int dc) {
     LDPC_REQUIRE(n > 0 && dv > 0 && dc > 1 && (long)n * dv % dc == 0 && (long)n * dv < (1L << 30),

@@ -24,11 +24,25 @@ void build_lane_layout(const HostGraph &h, int T, int VPT, std::vector<int32_t> 
 bool build_irr_layout(const HostGraph &h, int &VPT, int &KC, int &DC, int &S, int &P, std::vector<int32_t> &lane,
                       std::vector<int32_t> &cdeg);
 
+// Layer schedule of the layered (row-serial) decoder: the checks split into layers 0 .. L-1, no two
+// checks of a layer sharing a variable -- a deterministic colouring of the check-conflict graph
+// by kLayerRule.  layer[c]: the layer of check c; ptr [L+1] / chk [m]: the checks in (layer,
+// falling degree, id) order; tab / var: the kernel's tables (ldpc_internal.hpp, kLayerTab).
+// false (and L = 0) unless the graph is consistent, has 1 <= check degree <= 32 everywhere and no
+// check holds a variable twice.
+extern const char *const kLayerRule;
+struct LayerSchedule {
+    int L = 0, max_layer = 0;
+    std::vector<int32_t> layer, ptr, chk, tab, var;
+};
+bool build_layer_schedule(const HostGraph &h, LayerSchedule &S);
+
 // The soft-decoder layouts of a graph, built on the host: the arrays device_graph uploads.
 struct HostLayouts {
     std::vector<int32_t> lane_var, lane_slot, irr_lane, irr_cdeg;
     LocLayout loc;
     LocChainLayout chain;
+    LayerSchedule lay;
 };
 
 struct LayoutOptions {

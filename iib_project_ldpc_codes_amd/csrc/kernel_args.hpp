@@ -66,6 +66,24 @@ struct EnsArgs {
     int lds_slots;   // <*,gmem>: message slots [0, lds_slots) kept in LDS
 };
 
+// bp_layer_kernel: the layer schedule's tables (ldpc_graph::lay_*)
+struct LayerArgs {
+    const int32_t *tab, *var;
+    int n, m, E, B, L;
+    const float *llr;
+    float *post;
+    uint8_t *hard;
+    int32_t *its;
+    int max_iters;
+    float alpha;
+    // Monte-Carlo mode
+    ChanArgs ch;
+    uint64_t first_cw;
+    int32_t *trial;  // [B][max_iters+1]
+    float *scratch;  // <*,gmem>: one layer_block_bytes slab per workgroup
+    int lds_slots;   // <*,gmem>: block words [0, lds_slots) kept in LDS
+};
+
 inline ChanArgs make_chan(int kind, float p, float p2, uint64_t seed) {
     ChanArgs c;
     c.kind = kind;
@@ -84,6 +102,8 @@ hipError_t launch_loc_spa(const BpPlan &p, const ldpc_graph &g, BpArgs a, bool e
 hipError_t launch_loc_ms(const BpPlan &p, const ldpc_graph &g, BpArgs a, bool et, bool mc, hipStream_t s);
 hipError_t launch_irr(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, bool et, bool mc, hipStream_t s);
 hipError_t launch_generic(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, bool et, bool mc, hipStream_t s);
+// bp_layer_kernel (bp_layer.hip), from a bp_layer_plan
+hipError_t launch_layer(const BpPlan &p, LayerArgs a, int algo, bool et, bool mc, hipStream_t s);
 // BEC Monte-Carlo on a fixed code (bec.hip): launch_mc_decode's erasure-channel half
 hipError_t launch_mc_bec(const ldpc_graph &g, float p, float p2, uint64_t seed, uint64_t first_cw, int B,
                          int max_iters, int32_t *trial, int32_t *trial_its, hipStream_t stream);

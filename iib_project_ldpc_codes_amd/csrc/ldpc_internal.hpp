@@ -35,6 +35,9 @@ struct GraphShape {
     // Chained local-edge layout beside it (build_loc_chain_layout; fixed-count sum-product
     // decodes run on it); chn_Tq == 0: none
     int chn_Tq = 0, chn_words = 0;
+    // Layer schedule of bp_layer_kernel (build_layer_schedule, graph_host.cpp): lay_L layers, the
+    // largest of lay_max checks; lay_L == 0: none
+    int lay_L = 0, lay_max = 0;
 };
 
 // Device-resident Tanner graph: the shape and the device arrays (listed once more, each with the
@@ -58,6 +61,9 @@ struct ldpc_graph : GraphShape {
     int32_t *loc_info = nullptr;  // [2*KP][T] bit u + 4h: edge u present; bits 8+2h: local edge index jl;
                                   // bit 16 + 4h + jl: the same one-hot (min-sum order masks)
     int32_t *chn_var = nullptr, *chn_pos = nullptr, *chn_info = nullptr;  // the chained layout's, same formats
+    // layer schedule (LayerSchedule, graph_host.hpp): lay_tab [L][kLayerTab] per-layer offsets,
+    // lay_var [E] variables, layer-ordered and lane-major
+    int32_t *lay_tab = nullptr, *lay_var = nullptr;
 };
 
 // Local-edge layout (loc_layout.cpp): see the comment there.
@@ -235,7 +241,9 @@ hipError_t launch_bp_decode(const ldpc_graph &g, const float *d_llr, int B, int 
 enum class BpPath {
     Loc, Lds36, Irr, Generic8, Generic16, Generic32, GenericG8, GenericG16, GenericG32, None,
     // bp_ens_kernel (bp_ens_plan only; listed after None so the values above stay as they were)
-    Ens8, Ens16, Ens32, EnsG8, EnsG16, EnsG32
+    Ens8, Ens16, Ens32, EnsG8, EnsG16, EnsG32,
+    // bp_layer_kernel (bp_layer_plan only)
+    Layer8, Layer16, Layer32, LayerG8, LayerG16, LayerG32
 };
 struct BpPlan {
     BpPath path = BpPath::None;
@@ -261,6 +269,21 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop,
 // with the first lds_slots messages kept in LDS.  dc > 32: BpPath::None.
 BpPlan bp_ens_plan(int n, int dv, int dc, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
                    int cus);
+// The plan of a layered (row-serial) call (bp_layer_kernel, bp_layer.hip) on a graph with a layer
+// schedule (lay_L > 0; none: BpPath::None).  One workgroup owns one block
+//   posteriors P float[n] | check->variable messages R float[E]
+// (layer_block_bytes, 16-byte padded): wholly in LDS (256 threads, one workgroup per codeword)
+// when it fits gmem_plan's budget beside the Monte-Carlo curve, otherwise in a slab of the
+// scratch buffer, one per workgroup of the grid (1024 threads, one workgroup per CU), with the
+// block's first lds_slots words -- P first -- kept in LDS.
+BpPlan bp_layer_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
+                     int cus);
+constexpr size_t layer_block_bytes(size_t n, size_t E) { return ((n + E) * 4 + 15) & ~(size_t)15; }
+// Row l of lay_tab: [j] (j <= 32) = first word of the layer's j-th edges in lay_var (and in R): the
+// checks of a layer are sorted by falling degree, so position p of the layer has a j-th edge
+// exactly when p < [j + 1] - [j] (and [1] - [0] is the layer's number of checks); [32] is the
+// layer's end, the next row's [0].
+constexpr int kLayerMaxD = 32, kLayerTab = kLayerMaxD + 1;
 constexpr size_t ens_block_bytes(size_t n, size_t E) { return (E * 8 + n * 4 + 15) & ~(size_t)15; }
 // bp_generic_kernel's block: messages float[E] | channel LLRs float[n] | decision bytes u8[E]
 constexpr size_t generic_block_bytes(size_t n, size_t E) { return (E * 5 + n * 4 + 15) & ~(size_t)15; }
@@ -301,6 +324,18 @@ hipError_t launch_mc_ens(int n, int dv, int dc, const int32_t *check_lookup, con
                          int channel, float p, float p2, uint64_t seed, uint64_t first_cw, int B, int max_iters,
                          int algo, float alpha, int early_stop, int32_t *trial, int32_t *trial_its,
                          hipStream_t stream, float *d_scratch, size_t scratch_bytes);
+
+// Layered (row-serial) soft decoding on a fixed code (bp_layer.hip): the schedule of
+// graph_host.cpp's build_layer_schedule, semantics in include/ldpc_mi355x.h.  Scratch:
+// bp_layer_plan's; a shorter buffer is refused (hipErrorInvalidValue), a graph without a
+// schedule is hipErrorNotSupported.
+size_t layer_scratch_bytes(const ldpc_graph &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post);
+hipError_t launch_layer_decode(const ldpc_graph &g, const float *d_llr, int B, int max_iters, int algo, float alpha,
+                               int early_stop, float *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream,
+                               float *d_scratch, size_t scratch_bytes);
+hipError_t launch_mc_layer(const ldpc_graph &g, int channel, float p, float p2, uint64_t seed, uint64_t first_cw,
+                           int B, int max_iters, int algo, float alpha, int early_stop, int32_t *trial,
+                           int32_t *trial_its, hipStream_t stream, float *d_scratch, size_t scratch_bytes);
 
 // Buckets (= threads per workgroup) of the parallel graph sampler for n*dv
 // sockets; the permutation is in LDS (u16) when n*dv < 65536.  Must match

@@ -1,7 +1,8 @@
 """Batched decoders on the MI355X (device tensors via torch, host arrays via the C ABI).
 
 * ``bec_decode``  -- message_passing.c:7-82 over a batch of words (bit-exact).
-* ``bp_decode``   -- flooding sum-product / normalized min-sum (new capability).
+* ``bp_decode``   -- flooding sum-product / normalized min-sum (new capability);
+                     ``schedule="layered"``: the row-serial schedule of hardware decoders.
 * ``bp_ensemble_decode_dev`` -- the same decoders, word b on its own device-sampled graph b.
 * ``ml_decode``   -- ML ("optimal") erasure decoding, optimal_decode of
                      parallel_simulator.py:60-129 (GF(2) elimination on the device).
@@ -19,6 +20,18 @@ ALGOS = {"spa": ALGO_SPA, "sum-product": ALGO_SPA, "minsum": ALGO_MINSUM, "min-s
          ALGO_SPA: ALGO_SPA, ALGO_MINSUM: ALGO_MINSUM}
 CHANNELS = {"bec": CH_BEC, "bsc": CH_BSC, "awgn": CH_AWGN, "biawgn": CH_AWGN,
             CH_BEC: CH_BEC, CH_BSC: CH_BSC, CH_AWGN: CH_AWGN}
+SCHEDULES = ("flooding", "layered")
+
+
+def layer_rule():
+    """Name of the rule that colours a graph's checks into layers (snapshot.LAYER_RULE)."""
+    return _native.lib().ldpc_layer_rule().decode()
+
+
+def _schedule(schedule):
+    if schedule not in SCHEDULES:
+        raise ValueError(f"schedule must be one of {SCHEDULES}, not {schedule!r}")
+    return schedule
 
 
 def _torch():
@@ -126,10 +139,14 @@ def ml_ensemble_decode_dev(n, dv, dc, check_lookup, words, out=None, unsolved=No
 
 # ---------------------------------------------------------------------- soft
 def bp_decode_dev(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False, post=None, hard=None,
-                  its=None, stream=None, want_post=True, want_hard=True):
-    """llr: float32 [B, n] device tensor.  Returns (post, hard, its) device tensors."""
+                  its=None, stream=None, want_post=True, want_hard=True, schedule="flooding"):
+    """llr: float32 [B, n] device tensor.  Returns (post, hard, its) device tensors.
+    schedule: "flooding" (all checks, then all variables) or "layered" (row-serial: every check
+    works on the posteriors the checks before it updated, graph.layer_schedule() gives the
+    order; about half the iterations of flooding to converge)."""
     torch = _torch()
     B = llr.shape[0]
+    entry = "ldpc_bp_decode_batch_dev" if _schedule(schedule) == "flooding" else "ldpc_bp_layered_decode_batch_dev"
     assert llr.dtype == torch.float32 and llr.is_contiguous() and llr.shape[1] == graph.n
     if post is None and want_post:
         post = torch.empty_like(llr)
@@ -137,18 +154,18 @@ def bp_decode_dev(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False
         hard = torch.empty(llr.shape, dtype=torch.uint8, device=llr.device)
     if its is None:
         its = torch.empty((B,), dtype=torch.int32, device=llr.device)
-    rc = _native.lib().ldpc_bp_decode_batch_dev(graph.handle(), llr.data_ptr(), B, max_iters, ALGOS[algo],
-                                                float(alpha), int(bool(early_stop)), _ptr(post), _ptr(hard),
-                                                _ptr(its), _stream(stream))
-    _native.check(rc, "ldpc_bp_decode_batch_dev")
+    rc = getattr(_native.lib(), entry)(graph.handle(), llr.data_ptr(), B, max_iters, ALGOS[algo],
+                                       float(alpha), int(bool(early_stop)), _ptr(post), _ptr(hard),
+                                       _ptr(its), _stream(stream))
+    _native.check(rc, entry)
     return post, hard, its
 
 
-def bp_decode(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False):
+def bp_decode(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False, schedule="flooding"):
     """Host form: llr float32 [B, n] numpy.  Returns (post, hard, its) numpy."""
     torch = _torch()
     t = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(llr), dtype=np.float32)).cuda()
-    post, hard, its = bp_decode_dev(graph, t, max_iters, algo, alpha, early_stop)
+    post, hard, its = bp_decode_dev(graph, t, max_iters, algo, alpha, early_stop, schedule=schedule)
     torch.cuda.synchronize()
     return post.cpu().numpy(), hard.cpu().numpy(), its.cpu().numpy()
 

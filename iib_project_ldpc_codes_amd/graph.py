@@ -140,6 +140,21 @@ class TannerGraph:
         es = (2 if hard_only else 1) if early_stop else 0
         return _native.lib().ldpc_bp_kernel_name(self.handle(), es).decode()
 
+    def layer_schedule(self):
+        """The layer of every check in the layered decoder's schedule (int32[m], layers
+        0..L-1, no two checks of a layer share a variable; host only, no device needed).  A
+        layered decode equals a sequential sweep over the checks sorted by (layer, check id).
+        Raises LdpcError (LDPC_EUNSUP) for a graph without one: an empty check, a check degree
+        above 32, a check that holds a variable twice."""
+        cptr, cvar, vptr, vslot = [np.ascontiguousarray(a, np.int32) for a in self.to_csr()]
+        num = ct.c_int32(0)
+        layer = np.zeros(self.m, np.int32)
+        rc = _native.lib().ldpc_debug_layer_schedule(cptr.ctypes.data, cvar.ctypes.data, vptr.ctypes.data,
+                                                     vslot.ctypes.data, self.n, self.m, ct.addressof(num),
+                                                     layer.ctypes.data)
+        _native.check(rc, "ldpc_debug_layer_schedule")
+        return layer
+
     def __del__(self):
         try:
             if _native._lib is not None:

@@ -21,20 +21,22 @@ import time
 import numpy as np
 
 from . import _native
-from .decoder import ALGOS, CHANNELS
+from .decoder import ALGOS, CHANNELS, _schedule
 
 
 def device_executor(mc):
-    """Batch executor backed by ldpc_mc_batch_dev on the current HIP device."""
+    """Batch executor backed by ldpc_mc_batch_dev (mc.schedule "layered": ldpc_mc_layered_batch_dev)
+    on the current HIP device."""
     torch = mc.torch
+    entry = "ldpc_mc_layered_batch_dev" if mc.schedule == "layered" else "ldpc_mc_batch_dev"
 
     def run(first_cw, B, stop_frame_errors, counters, stream=None):
         s = stream if stream is not None else torch.cuda.current_stream()
-        rc = _native.lib().ldpc_mc_batch_dev(mc.graph.handle(), mc.channel, mc.param, mc.seed, int(first_cw),
-                                             int(B), mc.max_iters, mc.algo, mc.alpha, int(mc.early_stop),
-                                             mc.expurgation, int(stop_frame_errors), counters.data_ptr(),
-                                             s.cuda_stream)
-        _native.check(rc, "ldpc_mc_batch_dev")
+        rc = getattr(_native.lib(), entry)(mc.graph.handle(), mc.channel, mc.param, mc.seed, int(first_cw),
+                                           int(B), mc.max_iters, mc.algo, mc.alpha, int(mc.early_stop),
+                                           mc.expurgation, int(stop_frame_errors), counters.data_ptr(),
+                                           s.cuda_stream)
+        _native.check(rc, entry)
     return run
 
 
@@ -93,15 +95,24 @@ class MonteCarlo:
     optimal=True adds ML ("optimal") decoding of every trial's BEC word
     (parallel_simulator.py `optimal`, modes 1/2/4/5): counters_ml = [trials,
     ML frame errors, ML bit errors, 0, ML bit errors]; message_passing=False
-    drops the BP decode and the stop rule then counts ML frame errors."""
+    drops the BP decode and the stop rule then counts ML frame errors.
+
+    schedule="layered": the row-serial schedule (decoder.bp_decode_dev) on a fixed code, BSC and
+    BI-AWGN, on one rank or sharded; ensemble runs and the ML modes are flooding-only."""
 
     def __init__(self, graph, channel, param, max_iters, algo="spa", alpha=1.0, early_stop=True,
                  expurgation=-1, seed=0, batch=4096, process_group=None, executor=None, device=None,
-                 optimal=False, message_passing=True):
+                 optimal=False, message_passing=True, schedule="flooding"):
         import torch
         self.torch = torch
         self.graph = graph
         self.channel = CHANNELS[channel]
+        self.schedule = _schedule(schedule)
+        if self.schedule == "layered":
+            if isinstance(graph, _Ensemble):
+                raise ValueError("the layered schedule needs a fixed code: no host-built schedule per sampled graph")
+            if optimal or self.channel == CHANNELS["bec"]:
+                raise ValueError("the layered schedule decodes the BSC and the BI-AWGN channel (no BEC / ML modes)")
         self.param = float(param)
         self.max_iters = int(max_iters)
         self.algo = ALGOS[algo]

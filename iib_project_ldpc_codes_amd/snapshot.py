@@ -35,6 +35,13 @@ VERSION = 1
 SAMPLER_RULE = "one-level-rs/philox4x32-10<8192<=seq-draw-pair-words/philox4x32-7/split2<=393216"
 SAMPLER_RULE_R3 = "one-level-rs<8192<=seq-draw<=393216/philox4x32-10"
 
+# The layered decoder's schedule (csrc/graph_host.cpp build_layer_schedule: which layer a check
+# gets; ldpc_layer_rule() must name the same rule, tests/test_layer_schedule.py).  A layered run
+# records it: under another colouring the same trials decode differently, so a resumed run must
+# colour as its first part did.  Flooding runs record neither field, and a snapshot without the
+# schedule field -- every one written before it existed -- is a flooding run.
+LAYER_RULE = "first-fit/check-order+balance-to-mean/v1"
+
 
 def graph_fingerprint(graph):
     """Identity of the code a run decodes: the edge lists' digest, or the ensemble parameters
@@ -53,10 +60,13 @@ def graph_fingerprint(graph):
 
 
 def config(mc):
-    return {"graph": graph_fingerprint(mc.graph), "channel": int(mc.channel), "param": float(mc.param),
-            "max_iters": int(mc.max_iters), "algo": int(mc.algo), "alpha": float(mc.alpha),
-            "early_stop": bool(mc.early_stop), "expurgation": int(mc.expurgation),
-            "optimal": bool(mc.optimal), "message_passing": bool(mc.message_passing)}
+    cfg = {"graph": graph_fingerprint(mc.graph), "channel": int(mc.channel), "param": float(mc.param),
+           "max_iters": int(mc.max_iters), "algo": int(mc.algo), "alpha": float(mc.alpha),
+           "early_stop": bool(mc.early_stop), "expurgation": int(mc.expurgation),
+           "optimal": bool(mc.optimal), "message_passing": bool(mc.message_passing)}
+    if getattr(mc, "schedule", "flooding") == "layered":  # flooding snapshots stay as they always were
+        cfg.update({"schedule": "layered", "layer_rule": LAYER_RULE})
+    return cfg
 
 
 def from_counters(mc, g):

@@ -161,6 +161,38 @@ int ldpc_mc_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t se
                       int64_t stop_frame_errors, int64_t *d_counters, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Layered (row-serial) schedule on a fixed code (csrc/bp_layer.hip)       */
+/* ---------------------------------------------------------------------- */
+/*
+ * The schedule of hardware LDPC decoders ("turbo-decoding message passing"): the
+ * checks are split into layers 0..L-1, no two checks of a layer sharing a variable
+ * (ldpc_debug_layer_schedule), and every check works on posteriors the checks before
+ * it have already updated.  With P = posteriors float[n], R = check->variable
+ * messages float[E]:
+ *   P[v] = llr[v], R[e] = +0
+ *   iteration t = 1..max_iters:
+ *     for each check c in (layer, id) order, slots e_j, variables v_j:
+ *       x_j = P[v_j] - R[e_j];  r = check rule on x;  P[v_j] = x_j + r_j;  R[e_j] = r_j
+ *     hard[v] = P[v] < 0;  early_stop: hard satisfies every check -> stop, its = t
+ * (fp32, no contraction; min-sum is bit-exact with this text, the checks of a layer
+ * being independent).  Arguments, outputs, the NULL rules, B = 0 and max_iters = 0 as
+ * ldpc_bp_decode_batch_dev.  The schedule exists for every consistent graph with check
+ * degrees 1..32 in which no check holds a variable twice; any other graph: LDPC_EUNSUP.
+ */
+int ldpc_bp_layered_decode_batch_dev(const ldpc_graph *g, const float *d_llr, int B, int max_iters, int algo,
+                                     float alpha, int early_stop, float *d_post, uint8_t *d_hard,
+                                     int32_t *d_its, void *stream);
+/*
+ * ldpc_mc_batch_dev on the layered schedule, BSC and BI-AWGN (LDPC_CH_BEC:
+ * LDPC_EINVAL): curve[0] = channel errors, curve[t] = posteriors < 0 after
+ * iteration t, repeated after a stop; counters, expurgation and the sequential
+ * stop rule exactly as there.
+ */
+int ldpc_mc_layered_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t seed, uint64_t first_cw,
+                              int B, int max_iters, int algo, float alpha, int early_stop, int expurgation,
+                              int64_t stop_frame_errors, int64_t *d_counters, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* Whole Monte-Carlo run over several devices of one process */
 /* ---------------------------------------------------------------------- */
 /*
@@ -386,6 +418,26 @@ int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const
  */
 int ldpc_debug_ens_plan(int n, int dv, int dc, int count, const int32_t *calls, int cus, int64_t *out,
                         char *names);
+
+/*
+ * Host-only: the layer schedule of a CSR graph (csrc/graph_host.cpp build_layer_schedule): the
+ * number of layers and layer[c] of every check c (layer: int32[m], may be NULL).  LDPC_EUNSUP
+ * when the graph has none (an empty check, a check degree above 32, a check that holds a
+ * variable twice).
+ */
+int ldpc_debug_layer_schedule(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                              const int32_t *var_slot, int n, int m, int32_t *num_layers, int32_t *layer);
+/* The name of the rule ldpc_debug_layer_schedule colours by (a snapshot of a layered run records it). */
+const char *ldpc_layer_rule(void);
+
+/*
+ * Host-only: the launch plans of `count` layered calls on one CSR graph (csrc/bp_plan.cpp
+ * bp_layer_plan); calls / out / names as ldpc_debug_bp_plan, names
+ * bp_layer_kernel<8|16|32,lds|gmem>.  LDPC_EUNSUP when the graph has no layer schedule.
+ */
+int ldpc_debug_layer_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                          const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
+                          int64_t *out, char *names);
 
 /*
  * Host-only: the launch plans of `count` BEC erasure-decoding calls on a graph of n variables

@@ -7,6 +7,8 @@
         trial, parallel_simulator_expurgated.py), n=64800, BEC, 200 it, expurgation X=3;
         --channel bsc|awgn [--algo minsum|spa]: the same ensemble under soft decoding (50 it,
         early stop, no expurgation unless --expurgation is given)
+--schedule layered (cfg3, cfg4): the row-serial schedule of hardware decoders on the fixed code
+(decoder.bp_decode_dev; the ensemble has no layered form).
 One process per GPU: `--gpus N` starts the N ranks itself (decided before any HIP call, refused
 when fewer than N GPUs are visible -- iib_project_ldpc_codes_amd/launch.py, the same plan as
 bench.py), or runs as a rank of an external torchrun; trials shard by index, counters are
@@ -16,6 +18,7 @@ parallel_simulator.py:198), --trials, or --seconds.
   python scripts/fer_sweep.py cfg3 [--trials 1000000] [--seconds 60]
   python scripts/fer_sweep.py cfg4 --gpus 8 --seconds 300
   python scripts/fer_sweep.py ens --channel bsc --algo minsum --points 0.07,0.065
+  python scripts/fer_sweep.py cfg3 --schedule layered --points 0.07
 """
 import argparse
 import json
@@ -51,6 +54,8 @@ def parse(argv=None):
     ap.add_argument("--channel", choices=["bec", "bsc", "awgn"], default="bec", help="ens: the channel")
     ap.add_argument("--algo", choices=["spa", "minsum"], default=None,
                     help="ens on bsc / awgn: the decoder (default minsum on bsc, spa on awgn)")
+    ap.add_argument("--schedule", choices=["flooding", "layered"], default="flooding",
+                    help="cfg3 / cfg4: the decoding schedule (layered: row-serial, about half the iterations)")
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks, one process per GPU (default: torchrun's WORLD_SIZE, else 1); "
                          "without WORLD_SIZE the sweep starts them itself")
@@ -61,6 +66,8 @@ def parse(argv=None):
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if args.expurgation is None:
         args.expurgation = 3 if args.channel == "bec" else -1
+    if args.schedule == "layered" and args.config == "ens":
+        ap.error("--schedule layered needs a fixed code (cfg3, cfg4): no host-built schedule per sampled graph")
     return args
 
 
@@ -107,11 +114,12 @@ def main(argv=None):
                                      expurgation=args.expurgation, seed=args.seed, batch=batch)
         else:
             mc = MonteCarlo(g, channel, p, iters, algo=algo, alpha=alpha, early_stop=True, seed=args.seed,
-                            batch=batch)
+                            batch=batch, schedule=args.schedule)
         ck = None
         if args.checkpoint_dir:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
-            ck = os.path.join(args.checkpoint_dir, f"{args.config}_p={p}_seed={args.seed}_B={batch}.json")
+            tag = "" if args.schedule == "flooding" else "_" + args.schedule  # flooding keeps its file names
+            ck = os.path.join(args.checkpoint_dir, f"{args.config}{tag}_p={p}_seed={args.seed}_B={batch}.json")
             if os.path.exists(ck):
                 mc.restore(snapshot.load(ck))
         torch.cuda.synchronize()
@@ -126,6 +134,8 @@ def main(argv=None):
                    "frame_errors": res["frame_errors"], "fer": res["fer"], "ber": res["ber"],
                    "mean_iterations": res["iterations"] / max(res["num_tests"], 1),
                    "seconds": el, "codewords_per_s": (res["num_tests"] - trials0) / el}
+            if args.schedule != "flooding":
+                out["schedule"] = args.schedule
             if channel == "awgn":
                 out["ebn0_db"] = float(de.sigma_to_ebn0_db(p, rate))
             print(json.dumps(out), flush=True)
