@@ -387,6 +387,24 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         if constexpr (ET) {
             if (tid == 0) stop_flag[0] = stop_flag[1] = 0u;  // visible after the staging barrier
         }
+        // the chained layout's decodes issue every table load (L2) before the LLR copy (HBM), so
+        // the two latencies overlap; the others load after it (batched there: neutral to 0.5 % slower)
+        constexpr bool STG = CL > 0;
+        auto load_tabs = [&]() {
+#pragma unroll
+            for (int k = 0; k < KP; ++k) {
+#pragma unroll
+                for (int u = 0; u < DVN0; ++u) sp[2 * k][u] = load_sp(2 * k, u);
+#pragma unroll
+                for (int u = 0; u < DVN1; ++u)
+                    if (!(chained(2 * k + 1) && u == DVN1 - 1)) sp[2 * k + 1][u] = load_sp(2 * k + 1, u);
+            }
+        };
+        int vv[2 * VP];
+        if constexpr (STG) {
+            load_tabs();
+            load_vars(vv);
+        }
         int err0 = 0;
         if constexpr (MC) {
             for (int i = tid; i <= iters; i += T) curve[i] = 0;
@@ -405,25 +423,32 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         } else {
             if constexpr (MSET)
                 for (int i = tid; i < nsw; i += T) syn[i] = 0u;
-            for (int v = tid; v < n; v += T) msg[v] = to_msg<ALGO>(a.llr[(size_t)b * n + v]);
+            if constexpr (STG) {
+                // every variable is the local one of one check, so n <= 2 VP T: the copy is 2 VP
+                // loads per thread, all in flight at once (one HBM round trip; the loop below
+                // takes one per unrolled trip); a thread's entries past n read variable n - 1
+                float r[2 * VP];
+                const float *lb = a.llr + (size_t)b * n;
+                int t = tid;
+                asm volatile("" : "+v"(t));  // as ld_fresh: no index per entry held across the decode
+#pragma unroll
+                for (int i = 0; i < 2 * VP; ++i) r[i] = lb[min(t + i * T, n - 1)];
+#pragma unroll
+                for (int i = 0; i < 2 * VP; ++i)
+                    if (t + i * T < n) msg[t + i * T] = to_msg<ALGO>(r[i]);
+            } else {
+                for (int v = tid; v < n; v += T) msg[v] = to_msg<ALGO>(a.llr[(size_t)b * n + v]);
+            }
         }
         __syncthreads();
         if constexpr (MC) {
             const int w = wave_sum(err0);
             if ((tid & (kWave - 1)) == 0) atomicAdd(&curve[0], w);
         }
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-#pragma unroll
-            for (int u = 0; u < DVN0; ++u) sp[2 * k][u] = load_sp(2 * k, u);
-#pragma unroll
-            for (int u = 0; u < DVN1; ++u)
-                if (!(chained(2 * k + 1) && u == DVN1 - 1)) sp[2 * k + 1][u] = load_sp(2 * k + 1, u);
-        }
+        if constexpr (!STG) load_tabs();
         float2 L[VP];  // SPA: E = 2^channel (clamped); min-sum: channel LLR
-        if constexpr (MC) {  // (the other decodes: neutral to 0.5 % slower with the batch, registers)
-            int vv[2 * VP];
-            load_vars(vv);
+        if constexpr (MC || STG) {
+            if constexpr (!STG) load_vars(vv);
 #pragma unroll
             for (int v = 0; v < VP; ++v)
                 L[v] = make_float2(vv[2 * v] >= 0 ? msg[vv[2 * v]] : 0.0f, vv[2 * v + 1] >= 0 ? msg[vv[2 * v + 1]] : 0.0f);
@@ -439,7 +464,15 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         auto init = [&](auto dn_tag, int v) {
             constexpr int DN = decltype(dn_tag)::value;
             float2 w;
-            if constexpr (SPA) {
+            if constexpr (SPA && STG) {
+                // the wire value clamp(E, 2^-23, 2^23) from the one E = exp2(clamp(L, +-126)): v_exp_f32
+                // is monotone and exact at +-23, so this is exp2(clamp(L, +-23)) to the bit
+                // (scripts/diag/fixed_cost_probe.hip compares the two over every float)
+                L[v] = make_float2(__builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(L[v].x, -126.0f, 126.0f)),
+                                   __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(L[v].y, -126.0f, 126.0f)));
+                w = make_float2(__builtin_amdgcn_fmed3f(L[v].x, 0x1p-23f, 0x1p23f),
+                                __builtin_amdgcn_fmed3f(L[v].y, 0x1p-23f, 0x1p23f));
+            } else if constexpr (SPA) {
                 w = make_float2(__builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(L[v].x, -23.0f, 23.0f)),
                                 __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(L[v].y, -23.0f, 23.0f)));
                 if constexpr (ET)  // the channel decision in the LSB
@@ -727,22 +760,50 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         }
         // ---- posteriors (after the last check phase) and outputs ----
         // (variable ids re-read where needed: not kept live through the decode loop)
+        // Fixed-count decodes (FIX) make one pass over the tables here: the gathers take the
+        // loop's own packed positions (sp[][], still in registers), each variable id is loaded
+        // once (pid[], issued before the gathers: used only behind the barrier), and the clamped-E
+        // test is made once, a ballot over the thread's values: a wave that holds one (rare) takes
+        // the pass that substitutes the channel values (SUBST), the others a pass without the
+        // test.  The other decodes read the tables again per var pair.
+        constexpr bool FIX = !ET && !MC;
         float2 pr[VP];
-        auto post = [&](auto dn_tag, auto abs_tag, int v) {
+        int pid[2 * VP];
+        bool clamped = false;
+        if constexpr (FIX) {
+            load_vars(pid);
+            if constexpr (SPA) {
+#pragma unroll
+                for (int v = 0; v < VP; ++v)
+                    clamped |= fabsf(__builtin_amdgcn_logf(L[v].x)) >= 125.5f || fabsf(__builtin_amdgcn_logf(L[v].y)) >= 125.5f;
+            }
+        }
+        auto post = [&](auto dn_tag, auto abs_tag, auto subst_tag, int v) {
             constexpr int DN = decltype(dn_tag)::value;
+            constexpr bool SUBST = decltype(subst_tag)::value;
             uint32_t a0[DVA], a1[DVA], spv[DVA];
             float2 cv[DVA];
+            if constexpr (FIX) {
+                gather(dn_tag, abs_tag, v, sp[v], cv, a0, a1);
+            } else {
 #pragma unroll
-            for (int u = 0; u < DN; ++u)
-                if (!(chained(v) && u == DN - 1)) spv[u] = load_sp(v, u);
-            gather(dn_tag, abs_tag, v, spv, cv, a0, a1);
+                for (int u = 0; u < DN; ++u)
+                    if (!(chained(v) && u == DN - 1)) spv[u] = load_sp(v, u);
+                gather(dn_tag, abs_tag, v, spv, cv, a0, a1);
+            }
             if constexpr (SPA) {
                 float2 s;
                 // the channel term from the register-held E = 2^L: log2 E is L to ~1e-7 (no
                 // second 40 KB read of the codeword's LLRs); a clamped E (|LLR| > 87 nats) takes
                 // the input value itself
                 s = make_float2(__builtin_amdgcn_logf(L[v].x), __builtin_amdgcn_logf(L[v].y));
-                if (fabsf(s.x) >= 125.5f || fabsf(s.y) >= 125.5f) {
+                if constexpr (FIX) {
+                    if constexpr (SUBST) {
+                        const float *lb = a.llr + (size_t)b * n;
+                        if (fabsf(s.x) >= 125.5f && pid[2 * v] >= 0) s.x = to_msg<ALGO>(lb[pid[2 * v]]);
+                        if (fabsf(s.y) >= 125.5f && pid[2 * v + 1] >= 0) s.y = to_msg<ALGO>(lb[pid[2 * v + 1]]);
+                    }
+                } else if (fabsf(s.x) >= 125.5f || fabsf(s.y) >= 125.5f) {
                     const float *lb = a.llr + (size_t)b * n;
                     const int v0 = ld_fresh(a.loc_var, (v * 2 + 0) * T + tid);
                     const int v1 = ld_fresh(a.loc_var, (v * 2 + 1) * T + tid);
@@ -759,23 +820,54 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             }
             __builtin_amdgcn_sched_barrier(0);  // one var pair's gathers in flight (VGPR budget)
         };
+        if (FIX && SPA && __builtin_expect(__builtin_amdgcn_ballot_w64(clamped) != 0, 0)) {
 #pragma unroll
-        for (int k = 0; k < KP; ++k) {
-            post(int_c<DVN0>{}, bool_c<ABS0>{}, 2 * k);
-            post(int_c<DVN1>{}, bool_c<ABS1>{}, 2 * k + 1);
+            for (int k = 0; k < KP; ++k) {
+                post(int_c<DVN0>{}, bool_c<ABS0>{}, bool_c<true>{}, 2 * k);
+                post(int_c<DVN1>{}, bool_c<ABS1>{}, bool_c<true>{}, 2 * k + 1);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < KP; ++k) {
+                post(int_c<DVN0>{}, bool_c<ABS0>{}, bool_c<false>{}, 2 * k);
+                post(int_c<DVN1>{}, bool_c<ABS1>{}, bool_c<false>{}, 2 * k + 1);
+            }
         }
         __syncthreads();  // all gathers done before the staging overwrites messages
 #pragma unroll
         for (int v = 0; v < VP; ++v) {
-            const int v0 = ld_fresh(a.loc_var, (v * 2 + 0) * T + tid), v1 = ld_fresh(a.loc_var, (v * 2 + 1) * T + tid);
+            int v0, v1;
+            if constexpr (FIX) {
+                v0 = pid[2 * v];
+                v1 = pid[2 * v + 1];
+            } else {
+                v0 = ld_fresh(a.loc_var, (v * 2 + 0) * T + tid);
+                v1 = ld_fresh(a.loc_var, (v * 2 + 1) * T + tid);
+            }
             if (v0 >= 0) msg[v0] = pr[v].x;
             if (v1 >= 0) msg[v1] = pr[v].y;
         }
         __syncthreads();
-        for (int v = tid; v < n; v += T) {
-            const float s = msg[v];
-            if (a.post) a.post[(size_t)b * n + v] = s * Domain<ALGO>::out;
-            if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(s < 0.0f);
+        if constexpr (FIX) {  // n <= 2 VP T (see the LLR copy): every LDS read issued before the first store
+            float o[2 * VP];
+            int t = tid;
+            asm volatile("" : "+v"(t));  // as ld_fresh: no index per entry held across the decode
+#pragma unroll
+            for (int i = 0; i < 2 * VP; ++i) o[i] = msg[min(t + i * T, n - 1)];
+#pragma unroll
+            for (int i = 0; i < 2 * VP; ++i) {
+                const int v = t + i * T;
+                if (v < n) {
+                    if (a.post) a.post[(size_t)b * n + v] = o[i] * Domain<ALGO>::out;
+                    if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(o[i] < 0.0f);
+                }
+            }
+        } else {
+            for (int v = tid; v < n; v += T) {
+                const float s = msg[v];
+                if (a.post) a.post[(size_t)b * n + v] = s * Domain<ALGO>::out;
+                if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(s < 0.0f);
+            }
         }
         if (a.its && tid == 0) a.its[b] = iters;
     }
