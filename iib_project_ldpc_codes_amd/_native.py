@@ -20,6 +20,12 @@ MC_NCOUNT = 4
 _lib = None
 
 
+class Quant(ct.Structure):
+    """ldpc_quant of include/ldpc_mi355x.h (decoder.Quant builds it)."""
+    _fields_ = [("scale", ct.c_float), ("msg_bits", ct.c_int32), ("post_bits", ct.c_int32),
+                ("norm8", ct.c_int32), ("offset", ct.c_int32)]
+
+
 class LdpcError(RuntimeError):
     def __init__(self, func, rc, msg):
         super().__init__(f"{func} failed ({rc}): {msg}")
@@ -72,6 +78,10 @@ SIGNATURES = {
     "ldpc_debug_layer_schedule": ([P, P, P, P, i, i, P, P], i),
     "ldpc_layer_rule": ([], ct.c_char_p),
     "ldpc_debug_layer_plan": ([P, P, P, P, i, i, i, P, i, P, P], i),
+    "ldpc_bp_layered_q_decode_batch_dev": ([P, P, i, i, P, i, P, P, P, P], i),
+    "ldpc_mc_layered_q_batch_dev": ([P, i, f, u64, u64, i, i, P, i, i, i64, P, P], i),
+    "ldpc_debug_layer_q_plan": ([P, P, P, P, i, i, i, P, i, P, P], i),
+    "ldpc_quant_check": ([P], i),
     "ldpc_debug_seq_stats": ([P, i], i),
     "ldpc_debug_peel_stats": ([P, i], i),
     "ldpc_debug_peel_cap": ([i], i),

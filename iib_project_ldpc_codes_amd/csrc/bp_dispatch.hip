@@ -2,6 +2,7 @@
 // launch shape; the kernel families' own files (bp_lds.hip, bp_loc_*.hip, bp_irr.hip,
 // bp_generic.hip) launch from it.
 #include "kernel_args.hpp"
+#include "ldpc_mi355x.h"
 
 namespace ldpc {
 namespace {
@@ -135,6 +136,55 @@ hipError_t launch_mc_layer(const ldpc_graph &g, int channel, float p, float p2, 
     a.trial = trial;
     a.its = trial_its;
     return launch_layered(g, a, d_scratch, scratch_bytes, algo, early_stop != 0, true, stream);
+}
+
+// ---- fixed-point layered min-sum: one bp_layer_q_plan per call, bp_layer_q.hip launches from it
+namespace {
+
+hipError_t launch_layered_q(const ldpc_graph &g, LayerQArgs a, const ldpc_quant &q, bool et, bool mc, hipStream_t s) {
+    const BpPlan p = bp_layer_q_plan(g, a.B, a.max_iters, 1, et, mc, a.post != nullptr, device_cus());
+    if (p.path == BpPath::None || !g.lay_tab || !g.lay_var || !g.lay_cbase) return hipErrorNotSupported;
+    a.tab = g.lay_tab;
+    a.var = g.lay_var;
+    a.cbase = g.lay_cbase;
+    a.n = g.n;
+    a.m = g.m;
+    a.L = g.lay_L;
+    a.scale = q.scale;
+    a.Q = (1 << (q.msg_bits - 1)) - 1;
+    a.Pmax = (1 << (q.post_bits - 1)) - 1;
+    a.norm8 = q.norm8;
+    a.offset = q.offset;
+    return launch_layer_q(p, a, et, mc, s);
+}
+
+}  // namespace
+
+hipError_t launch_layer_q_decode(const ldpc_graph &g, const float *d_llr, int B, int max_iters, const ldpc_quant &q,
+                                 int early_stop, int8_t *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream) {
+    if (B <= 0) return hipSuccess;
+    LayerQArgs a{};
+    a.B = B;
+    a.max_iters = max_iters;
+    a.llr = d_llr;
+    a.post = d_post;
+    a.hard = d_hard;
+    a.its = d_its;
+    return launch_layered_q(g, a, q, early_stop != 0, false, stream);
+}
+
+hipError_t launch_mc_layer_q(const ldpc_graph &g, int channel, float p, float p2, uint64_t seed, uint64_t first_cw,
+                             int B, int max_iters, const ldpc_quant &q, int early_stop, int32_t *trial,
+                             int32_t *trial_its, hipStream_t stream) {
+    if (B <= 0) return hipSuccess;
+    LayerQArgs a{};
+    a.B = B;
+    a.max_iters = max_iters;
+    a.ch = make_chan(channel, p, p2, seed);
+    a.first_cw = first_cw;
+    a.trial = trial;
+    a.its = trial_its;
+    return launch_layered_q(g, a, q, early_stop != 0, true, stream);
 }
 
 }  // namespace ldpc

@@ -1,0 +1,233 @@
+// bp_layer_q_kernel: fixed-point layered min-sum with compressed check records, on any graph with
+// a layer schedule whose block fits LDS (bp_layer_q_plan), and its launch ladder.  Semantics:
+// include/ldpc_mi355x.h, ldpc_bp_layered_q_decode_batch_dev -- every value an integer, so the
+// kernel is bit-exact with that text.
+//
+// One workgroup decodes one codeword at a time on a block
+//   posteriors P int8[n] (padded to 4 bytes) | one record per check, in layer order
+// in LDS.  The record holds what the check's messages R are rebuilt from: the two magnitudes
+// f(m1) and f(m2), the index i1 of the first minimum and one sign bit per edge --
+//   check degree <= 16: one word   f(m1) | f(m2) << 6 | i1 << 12 | signs << 16
+//   check degree <= 32: two words  f(m1) | f(m2) << 6 | i1 << 12,  signs
+// (magnitudes <= Q <= 63).  Record lay_cbase[l] + p belongs to the check at position p of layer l,
+// so the threads of a wave read neighbouring records.  As in bp_layer.hip thread i takes positions
+// i, i + T, ... of a layer and one workgroup barrier ends the layer; the checks of a layer share no
+// variable, so the byte stores to P of different threads never touch the same byte.
+#include "bp_device.hpp"
+
+namespace ldpc {
+namespace {
+
+typedef __attribute__((address_space(3))) signed char lds_i8;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+
+// The channel quantiser: rint_half_even(clamp(l * scale, -Q, +Q)), NaN -> 0 (one fp32 product;
+// the library is built without contraction)
+__device__ __forceinline__ int quantise(float l, float scale, int Q) {
+    const float t = l * scale;
+    if (t != t) return 0;
+    return (int)__builtin_rintf(fminf(fmaxf(t, (float)-Q), (float)Q));
+}
+
+template <int T, int MAXDC, bool ET, bool MC>
+__global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int RW = MAXDC <= 16 ? 1 : 2;            // words of a record
+    constexpr uint32_t IMASK = MAXDC <= 16 ? 15 : 31;  // the index field
+    const int tid = threadIdx.x;
+    const int n = a.n, m = a.m, iters = a.max_iters, L = a.L;
+    const int Q = a.Q, Pmax = a.Pmax, norm8 = a.norm8, offset = a.offset;
+    const int n4 = (n + 3) >> 2;  // words of P
+    // LDS: curve (16-byte padded, Monte-Carlo only) | P | records
+    const size_t curve_pad = MC ? curve_bytes(iters) : 0;
+    int *curve = reinterpret_cast<int *>(smem);
+    lds_i8 *P = (lds_i8 *)((lds_u8 *)smem + curve_pad);
+    lds_u32 *Pw = (lds_u32 *)P;
+    lds_u32 *rec = Pw + n4;
+    // Monte-Carlo: bit errors of the workgroup's decisions into curve[i]
+    auto count = [&](int i, int errs) {
+        if (MC) {
+            const int w = wave_sum(errs);
+            if ((tid & (kWave - 1)) == 0) atomicAdd(&curve[i], w);
+        }
+    };
+    auto f = [&](int mag) { return max(((mag * norm8) >> 3) - offset, 0); };
+
+    // Variables and degree of the check at position p of a layer (bp_layer.hip's load_vars)
+    auto load_vars = [&](const int32_t *row, int p, int &d, int (&v)[MAXDC]) {
+        d = 0;
+#pragma unroll
+        for (int j = 0; j < MAXDC; ++j) {
+            const bool has = p < row[j + 1] - row[j];
+            v[j] = has ? a.var[row[j] + p] : 0;
+            d += has;
+        }
+    };
+    // The check with record c, degree d > 0 and variables v: every load before the first use
+    auto step = [&](int c, int d, const int (&v)[MAXDC]) {
+        int x[MAXDC];
+#pragma unroll
+        for (int j = 0; j < MAXDC; ++j) x[j] = P[v[j]];  // an absent edge reads byte 0
+        const uint32_t w0 = rec[c * RW];
+        const uint32_t sg = RW == 2 ? rec[c * RW + 1] : w0 >> 16;
+        const int f1 = w0 & 63, f2 = (w0 >> 6) & 63, i1 = (w0 >> 12) & IMASK;
+        // x_j = P - R_j, R_j rebuilt from the record; the min1 / min2 / index scan (an absent
+        // edge enters as magnitude Q, positive: it lowers neither minimum and is never first)
+        int a_[MAXDC];
+        uint32_t neg = 0;
+#pragma unroll
+        for (int j = 0; j < MAXDC; ++j) {
+            const int mag = j == i1 ? f2 : f1;
+            x[j] -= (sg >> j) & 1 ? -mag : mag;
+            const bool has = j < d;
+            a_[j] = has ? min(abs(x[j]), Q) : Q;
+            neg |= (uint32_t)(has && x[j] < 0) << j;
+        }
+        int m1 = a_[0], m2 = Q, k1 = 0;
+#pragma unroll
+        for (int j = 1; j < MAXDC; ++j) {
+            const bool lt = a_[j] < m1;
+            m2 = lt ? m1 : min(m2, a_[j]);
+            k1 = lt ? j : k1;
+            m1 = lt ? a_[j] : m1;
+        }
+        const int g1 = f(m1), g2 = f(m2);
+        const uint32_t par = __builtin_popcount(neg) & 1;
+        // r_j is negative iff parity ^ s_j, and |r_j| > 0
+        uint32_t rs = (par ? ~neg : neg) & (d >= 32 ? 0xFFFFFFFFu : (1u << d) - 1u);
+        if (g1 == 0) rs &= 1u << k1;
+        if (g2 == 0) rs &= ~(1u << k1);
+#pragma unroll
+        for (int j = 0; j < MAXDC; ++j)
+            if (j < d) {
+                const int mag = j == k1 ? g2 : g1;
+                const int r = (rs >> j) & 1 ? -mag : mag;
+                P[v[j]] = (signed char)min(max(x[j] + r, -Pmax), Pmax);
+            }
+        const uint32_t head = (uint32_t)g1 | (uint32_t)g2 << 6 | (uint32_t)k1 << 12;
+        if constexpr (RW == 2) {
+            rec[c * RW] = head;
+            rec[c * RW + 1] = rs;
+        } else {
+            rec[c] = head | rs << 16;
+        }
+    };
+    // negative bytes of P word w (the padding bytes stay 0)
+    auto neg_bytes = [&](int w) { return __builtin_popcount(Pw[w] & 0x80808080u); };
+    // the first step of the next layer, loaded ahead of the barrier that ends this one (the index
+    // reads wait for nothing the layer writes); above degree 8 the registers go to the check rule
+    constexpr bool PF = MAXDC <= 8;
+    int dn = 0, vn[MAXDC];
+
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const uint64_t cw = a.first_cw + (uint64_t)b;
+        __syncthreads();  // previous codeword fully drained
+        if (MC) {
+            for (int i = tid; i <= iters; i += T) curve[i] = 0;
+        }
+        for (int v = n + tid; v < 4 * n4; v += T) P[v] = 0;  // the padding bytes
+        int err0 = 0;
+        for (int v = tid; v < n; v += T) {
+            const float l = MC ? chan_soft(a.ch, cw, v) : a.llr[(size_t)b * n + v];
+            const int c = quantise(l, a.scale, Q);
+            P[v] = (signed char)c;
+            err0 += (c < 0);
+            if (!MC && iters == 0) {  // no iteration: the quantised channel values themselves
+                if (a.post) a.post[(size_t)b * n + v] = (int8_t)c;
+                if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(c < 0);
+            }
+        }
+        for (int i = tid; i < m * RW; i += T) rec[i] = 0;  // R = 0
+        __syncthreads();
+        count(0, err0);
+        int it = 0;
+        if constexpr (PF) load_vars(a.tab, tid, dn, vn);
+        while (it < iters) {
+            for (int l = 0; l < L; ++l) {
+                const int32_t *row = a.tab + (size_t)l * kLayerTab;  // wave-uniform: scalar loads
+                const int cnt = row[1] - row[0];                     // every check has a first edge
+                const int cb = a.cbase[l];
+                int p = tid;
+                if constexpr (PF) {  // the first step's indices are here already
+                    if (dn > 0) step(cb + p, dn, vn);
+                    p += T;
+                }
+                for (; p < cnt; p += T) {
+                    int d, v[MAXDC];
+                    load_vars(row, p, d, v);
+                    step(cb + p, d, v);
+                }
+                // the next layer's first step (after the last layer: the next iteration's or codeword's)
+                if constexpr (PF) load_vars(a.tab + (size_t)(l + 1 == L ? 0 : l + 1) * kLayerTab, tid, dn, vn);
+                __syncthreads();  // the layer's posteriors, before the next layer gathers them
+            }
+            ++it;
+            if (MC) {
+                int errs = 0;
+                for (int w = tid; w < n4; w += T) errs += neg_bytes(w);
+                count(it, errs);
+            }
+            if constexpr (ET) {
+                // the syndrome of the decisions, on the layers' tables (nothing is written: no barrier between layers)
+                int unsat = 0;
+                for (int l = 0; l < L; ++l) {
+                    const int32_t *row = a.tab + (size_t)l * kLayerTab;
+                    const int cnt = row[1] - row[0];
+                    for (int p = tid; p < cnt; p += T) {
+                        int vv[MAXDC];
+#pragma unroll
+                        for (int j = 0; j < MAXDC; ++j) vv[j] = p < row[j + 1] - row[j] ? a.var[row[j] + p] : -1;
+                        int par = 0;
+#pragma unroll
+                        for (int j = 0; j < MAXDC; ++j) par ^= (int)(vv[j] >= 0) & (int)(P[max(vv[j], 0)] < 0);
+                        unsat |= par;
+                    }
+                }
+                if (!__syncthreads_or(unsat)) break;
+            } else if (MC) {
+                __syncthreads();  // the count has read P: the next iteration's first layer may write it
+            }
+        }
+        __syncthreads();
+        if (!MC && iters > 0) {
+            for (int v = tid; v < n; v += T) {
+                const int s = P[v];
+                if (a.post) a.post[(size_t)b * n + v] = (int8_t)s;
+                if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(s < 0);
+            }
+        }
+        if (MC) {
+            int32_t *tr = a.trial + (size_t)b * (iters + 1);
+            const int last = curve[it];
+            for (int i = tid; i <= iters; i += T) tr[i] = i <= it ? curve[i] : last;
+        }
+        if ((MC || a.its) && tid == 0) a.its[b] = it;
+    }
+}
+
+template <int MAXDC>
+hipError_t launch_layer_q_shape(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s) {
+    constexpr int T = 256;
+    if (p.threads != T) return hipErrorInvalidValue;
+    auto go = [&](auto k) {
+        const hipError_t e = allow_lds(k, p.lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k, dim3(p.grid), dim3(T), p.lds, s, a);
+        return hipGetLastError();
+    };
+    if (et) return mc ? go(bp_layer_q_kernel<T, MAXDC, true, true>) : go(bp_layer_q_kernel<T, MAXDC, true, false>);
+    return mc ? go(bp_layer_q_kernel<T, MAXDC, false, true>) : go(bp_layer_q_kernel<T, MAXDC, false, false>);
+}
+
+}  // namespace
+
+hipError_t launch_layer_q(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s) {
+    switch (p.path) {
+        case BpPath::LayerQ8: return launch_layer_q_shape<8>(p, a, et, mc, s);
+        case BpPath::LayerQ16: return launch_layer_q_shape<16>(p, a, et, mc, s);
+        case BpPath::LayerQ32: return launch_layer_q_shape<32>(p, a, et, mc, s);
+        default: return hipErrorNotSupported;
+    }
+}
+
+}  // namespace ldpc

@@ -261,4 +261,26 @@ BpPlan bp_layer_plan(const GraphShape &g, int B, int iters, int /*algo*/, bool /
     return p;
 }
 
+// bp_layer_q_kernel: the graph's layer schedule and its size decide; the block is in LDS or
+// there is no kernel.  algo (min-sum only), early stop and want_post do not enter the layout.
+BpPlan bp_layer_q_plan(const GraphShape &g, int B, int iters, int /*algo*/, bool /*early_stop*/, bool mc,
+                       bool /*want_post*/, int /*cus*/) {
+    BpPlan p;
+    if (!g.consistent || g.lay_L <= 0 || g.max_cdeg > kLayerMaxD) return p;
+    const size_t lds = (mc ? curve_bytes(iters) : 0) + (((size_t)g.n + 3) & ~(size_t)3) +
+                       layer_q_record_bytes(g.max_cdeg) * (size_t)g.m;
+    if (lds > kLdsMax - 4096) return p;  // gmem_plan's budget; no slab form
+    const int w = g.max_cdeg <= 8 ? 0 : (g.max_cdeg <= 16 ? 1 : 2);
+    static const BpPath paths[3] = {BpPath::LayerQ8, BpPath::LayerQ16, BpPath::LayerQ32};
+    static const char *const names[3] = {"bp_layer_q_kernel<8>", "bp_layer_q_kernel<16>", "bp_layer_q_kernel<32>"};
+    p.path = paths[w];
+    p.name = names[w];
+    p.threads = 256;
+    p.grid = B;
+    p.lds = lds;
+    // a CU holds 32 waves (8 per SIMD) = eight 256-thread workgroups, and kLdsMax bytes of LDS
+    p.wg_per_cu = (int)std::min<size_t>(8, kLdsMax / lds);
+    return p;
+}
+
 }  // namespace ldpc

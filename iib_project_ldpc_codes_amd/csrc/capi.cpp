@@ -3,6 +3,7 @@
 // cache graph_device.cpp, the workspaces workspace.hpp.  Each synchronous host-pointer form
 // stages into its workspace and shares the launches with its device-pointer (_dev) twin.  There
 // is no CPU compute path: without a visible HIP device every entry point fails with LDPC_ENODEV.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -542,6 +543,83 @@ int ldpc_debug_layer_plan(const int32_t *check_ptr, const int32_t *check_var, co
         const int32_t *c = calls + 6 * (size_t)i;
         LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
         write_plan(bp_layer_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus), i, out, names);
+    }
+    return LDPC_OK;
+}
+
+// --------------------------- fixed-point layered min-sum -------------------
+int ldpc_quant_check(const ldpc_quant *q) {
+    LDPC_REQUIRE(q, "null ldpc_quant");
+    LDPC_REQUIRE(q->msg_bits >= 2 && q->msg_bits <= 7, "ldpc_quant: need 2 <= msg_bits <= 7");
+    LDPC_REQUIRE(q->post_bits >= q->msg_bits && q->post_bits <= 8, "ldpc_quant: need msg_bits <= post_bits <= 8");
+    LDPC_REQUIRE(q->norm8 >= 1 && q->norm8 <= 8, "ldpc_quant: need 1 <= norm8 <= 8");
+    LDPC_REQUIRE(q->offset >= 0 && q->offset <= (1 << (q->msg_bits - 1)) - 1, "ldpc_quant: need 0 <= offset <= Q");
+    LDPC_REQUIRE(std::isfinite(q->scale) && q->scale > 0.0f, "ldpc_quant: scale must be finite and > 0");
+    return LDPC_OK;
+}
+
+// The checks the two fixed-point entries share; LDPC_EUNSUP for a graph without a schedule or
+// with a block beyond LDS
+static int layered_q_check(const ldpc_graph *g, const ldpc_quant *q, int B, int max_iters, bool mc) {
+    LDPC_TRY(ldpc_quant_check(q));
+    LDPC_TRY(layered_check(g, LDPC_ALGO_MINSUM));
+    if (bp_layer_q_plan(*g, B, max_iters, 1, false, mc, false, 1).path == BpPath::None) {
+        set_error("the fixed-point layered block (posteriors and check records) does not fit LDS");
+        return LDPC_EUNSUP;
+    }
+    return LDPC_OK;
+}
+
+int ldpc_bp_layered_q_decode_batch_dev(const ldpc_graph *g, const float *d_llr, int B, int max_iters,
+                                       const ldpc_quant *q, int early_stop, int8_t *d_post, uint8_t *d_hard,
+                                       int32_t *d_its, void *stream) {
+    LDPC_REQUIRE(g && (B == 0 || d_llr) && B >= 0 && max_iters >= 0, "bad soft batch arguments");
+    LDPC_TRY(layered_q_check(g, q, B, max_iters, false));
+    if (B == 0) return LDPC_OK;
+    LDPC_HIP(launch_layer_q_decode(*g, d_llr, B, max_iters, *q, early_stop, d_post, d_hard, d_its,
+                                   static_cast<hipStream_t>(stream)));
+    return LDPC_OK;
+}
+
+int ldpc_mc_layered_q_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t seed, uint64_t first_cw,
+                                int B, int max_iters, const ldpc_quant *q, int early_stop, int expurgation,
+                                int64_t stop_frame_errors, int64_t *d_counters, void *stream) {
+    LDPC_REQUIRE(g && d_counters && B >= 0 && max_iters >= 0, "bad MC arguments");
+    LDPC_REQUIRE(channel != LDPC_CH_BEC, "the layered schedule decodes the BSC and the BI-AWGN channel (BEC: ldpc_mc_batch_dev)");
+    float p, p2;
+    LDPC_TRY(channel_params(channel, param, &p, &p2));
+    LDPC_TRY(layered_q_check(g, q, B, max_iters, true));
+    if (B == 0) return LDPC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only: devices launch in parallel
+    std::lock_guard<std::mutex> wl(ws.mu);
+    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
+    int32_t *cut = ws.cutoff.get<int32_t>(4);
+    LDPC_ALLOCATED(trial && its && cut);
+    LDPC_HIP(launch_mc_layer_q(*g, channel, p, p2, seed, first_cw, B, max_iters, *q, early_stop, trial, its, s));
+    LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
+    return LDPC_OK;
+}
+
+int ldpc_debug_layer_q_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                            const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
+                            char *names) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
+    HostGraph h;
+    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
+    GraphShape g;
+    HostLayouts L;
+    host_layouts(h, g, L, true, layout_options());
+    if (g.lay_L <= 0) {
+        set_error(kNoSchedule);
+        return LDPC_EUNSUP;
+    }
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 6 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        const BpPlan p = bp_layer_q_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus);
+        write_plan(p, i, out, names);
+        out[9 * (size_t)i + 4] = p.wg_per_cu;
     }
     return LDPC_OK;
 }

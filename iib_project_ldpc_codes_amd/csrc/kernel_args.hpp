@@ -84,6 +84,23 @@ struct LayerArgs {
     int lds_slots;   // <*,gmem>: block words [0, lds_slots) kept in LDS
 };
 
+// bp_layer_q_kernel: the layer schedule's tables and the quantiser (ldpc_quant, validated)
+struct LayerQArgs {
+    const int32_t *tab, *var, *cbase;  // cbase [L]: the record of a layer's first check
+    int n, m, B, L;
+    const float *llr;
+    int8_t *post;
+    uint8_t *hard;
+    int32_t *its;
+    int max_iters;
+    float scale;
+    int Q, Pmax, norm8, offset;
+    // Monte-Carlo mode
+    ChanArgs ch;
+    uint64_t first_cw;
+    int32_t *trial;  // [B][max_iters+1]
+};
+
 inline ChanArgs make_chan(int kind, float p, float p2, uint64_t seed) {
     ChanArgs c;
     c.kind = kind;
@@ -104,6 +121,8 @@ hipError_t launch_irr(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, 
 hipError_t launch_generic(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, bool et, bool mc, hipStream_t s);
 // bp_layer_kernel (bp_layer.hip), from a bp_layer_plan
 hipError_t launch_layer(const BpPlan &p, LayerArgs a, int algo, bool et, bool mc, hipStream_t s);
+// bp_layer_q_kernel (bp_layer_q.hip), from a bp_layer_q_plan
+hipError_t launch_layer_q(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s);
 // BEC Monte-Carlo on a fixed code (bec.hip): launch_mc_decode's erasure-channel half
 hipError_t launch_mc_bec(const ldpc_graph &g, float p, float p2, uint64_t seed, uint64_t first_cw, int B,
                          int max_iters, int32_t *trial, int32_t *trial_its, hipStream_t stream);

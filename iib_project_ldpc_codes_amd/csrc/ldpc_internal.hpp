@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+struct ldpc_quant;  // include/ldpc_mi355x.h
+
 // Shape of a prepared Tanner graph: every scalar of the graph and of its kernel layouts, filled
 // on the host (host_layouts, graph_host.cpp).  All that the launch plan (bp_plan.cpp) and the
 // launchers' sizing read; no device is involved.  Slot e = position in the check-major edge
@@ -64,6 +66,7 @@ struct ldpc_graph : GraphShape {
     // layer schedule (LayerSchedule, graph_host.hpp): lay_tab [L][kLayerTab] per-layer offsets,
     // lay_var [E] variables, layer-ordered and lane-major
     int32_t *lay_tab = nullptr, *lay_var = nullptr;
+    int32_t *lay_cbase = nullptr;  // [L+1] checks before each layer (LayerSchedule::ptr): bp_layer_q_kernel's record base
 };
 
 // Local-edge layout (loc_layout.cpp): see the comment there.
@@ -243,7 +246,9 @@ enum class BpPath {
     // bp_ens_kernel (bp_ens_plan only; listed after None so the values above stay as they were)
     Ens8, Ens16, Ens32, EnsG8, EnsG16, EnsG32,
     // bp_layer_kernel (bp_layer_plan only)
-    Layer8, Layer16, Layer32, LayerG8, LayerG16, LayerG32
+    Layer8, Layer16, Layer32, LayerG8, LayerG16, LayerG32,
+    // bp_layer_q_kernel (bp_layer_q_plan only)
+    LayerQ8, LayerQ16, LayerQ32
 };
 struct BpPlan {
     BpPath path = BpPath::None;
@@ -256,6 +261,7 @@ struct BpPlan {
     size_t slab = 0;            // bytes of per-workgroup slabs at the start of scratch (0: none)
     long counter = -1;          // byte offset of the work counter in scratch (-1: none)
     size_t scratch = 0;         // total scratch bytes the launch needs
+    int wg_per_cu = 0;          // bp_layer_q_kernel: workgroups a CU holds at once (LDS and wave slots)
 };
 // cus: compute units of the device (device_cus()); mc: fused-channel Monte-Carlo; want_post: a
 // decode that returns posteriors.
@@ -278,6 +284,15 @@ BpPlan bp_ens_plan(int n, int dv, int dc, int B, int iters, int algo, bool early
 // block's first lds_slots words -- P first -- kept in LDS.
 BpPlan bp_layer_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
                      int cus);
+// The plan of a fixed-point layered call (bp_layer_q_kernel, bp_layer_q.hip).  One workgroup (256
+// threads, one per codeword) owns, after the 16-byte padded Monte-Carlo curve, the block
+//   posteriors P int8[n], padded to 4 bytes | one record per check
+// (layer_q_record_bytes: 4 bytes up to check degree 16, 8 up to 32) wholly in LDS.  There is no
+// slab form: a block past gmem_plan's budget (160 KiB - 4 KiB) has no plan (BpPath::None), as has
+// a graph without a layer schedule.  wg_per_cu: how many such workgroups one CU holds.
+BpPlan bp_layer_q_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
+                       int cus);
+constexpr size_t layer_q_record_bytes(int max_cdeg) { return max_cdeg <= 16 ? 4 : 8; }
 constexpr size_t layer_block_bytes(size_t n, size_t E) { return ((n + E) * 4 + 15) & ~(size_t)15; }
 // Row l of lay_tab: [j] (j <= 32) = first word of the layer's j-th edges in lay_var (and in R): the
 // checks of a layer are sorted by falling degree, so position p of the layer has a j-th edge
@@ -336,6 +351,14 @@ hipError_t launch_layer_decode(const ldpc_graph &g, const float *d_llr, int B, i
 hipError_t launch_mc_layer(const ldpc_graph &g, int channel, float p, float p2, uint64_t seed, uint64_t first_cw,
                            int B, int max_iters, int algo, float alpha, int early_stop, int32_t *trial,
                            int32_t *trial_its, hipStream_t stream, float *d_scratch, size_t scratch_bytes);
+
+// Fixed-point layered min-sum (bp_layer_q.hip), semantics in include/ldpc_mi355x.h; q validated by
+// the caller.  No scratch.  hipErrorNotSupported: no schedule, or the block does not fit LDS.
+hipError_t launch_layer_q_decode(const ldpc_graph &g, const float *d_llr, int B, int max_iters, const ldpc_quant &q,
+                                 int early_stop, int8_t *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream);
+hipError_t launch_mc_layer_q(const ldpc_graph &g, int channel, float p, float p2, uint64_t seed, uint64_t first_cw,
+                             int B, int max_iters, const ldpc_quant &q, int early_stop, int32_t *trial,
+                             int32_t *trial_its, hipStream_t stream);
 
 // Buckets (= threads per workgroup) of the parallel graph sampler for n*dv
 // sockets; the permutation is in LDS (u16) when n*dv < 65536.  Must match

@@ -34,6 +34,66 @@ def _schedule(schedule):
     return schedule
 
 
+class Quant:
+    """Parameters of the fixed-point layered min-sum (ldpc_quant, include/ldpc_mi355x.h): `bits`-bit
+    messages (magnitudes up to Q = 2^(bits-1) - 1), `post_bits`-bit saturating posteriors, channel
+    LLRs quantised as rint(clamp(llr * scale, -Q, Q)), check magnitudes f(m) = max(((m * norm8) >> 3)
+    - offset, 0).  Valid: 2 <= bits <= 7, bits <= post_bits <= 8, 1 <= norm8 <= 8, 0 <= offset <= Q,
+    scale finite and > 0 (ValueError otherwise)."""
+    FIELDS = ("bits", "post_bits", "scale", "norm8", "offset")
+
+    def __init__(self, bits, post_bits, scale, norm8=6, offset=0):
+        for name, x in (("bits", bits), ("post_bits", post_bits), ("norm8", norm8), ("offset", offset)):
+            if isinstance(x, bool) or int(x) != x:
+                raise ValueError(f"Quant: {name} must be an integer, not {x!r}")
+        self.bits, self.post_bits, self.norm8, self.offset = int(bits), int(post_bits), int(norm8), int(offset)
+        self.scale = float(np.float32(scale))
+        if not 2 <= self.bits <= 7:
+            raise ValueError("Quant: need 2 <= bits <= 7")
+        if not self.bits <= self.post_bits <= 8:
+            raise ValueError("Quant: need bits <= post_bits <= 8")
+        if not 1 <= self.norm8 <= 8:
+            raise ValueError("Quant: need 1 <= norm8 <= 8")
+        if not 0 <= self.offset <= self.Q:
+            raise ValueError("Quant: need 0 <= offset <= Q = 2^(bits-1) - 1")
+        if not (np.isfinite(self.scale) and self.scale > 0):
+            raise ValueError("Quant: scale must be finite and > 0 (as a float32)")
+
+    @property
+    def Q(self):
+        return (1 << (self.bits - 1)) - 1
+
+    @property
+    def Pmax(self):
+        return (1 << (self.post_bits - 1)) - 1
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    def native(self):
+        return _native.Quant(self.scale, self.bits, self.post_bits, self.norm8, self.offset)
+
+    def __eq__(self, other):
+        return isinstance(other, Quant) and self.as_dict() == other.as_dict()
+
+    def __hash__(self):
+        return hash(tuple(self.as_dict().items()))
+
+    def __repr__(self):
+        return "Quant(%d, %d, %r, norm8=%d, offset=%d)" % (self.bits, self.post_bits, self.scale, self.norm8, self.offset)
+
+
+def _quant(quant, schedule, algo):
+    """None, or the Quant of a call: it needs the layered schedule and min-sum."""
+    if quant is None:
+        return None
+    if not isinstance(quant, Quant):
+        raise ValueError(f"quant must be a decoder.Quant, not {quant!r}")
+    if _schedule(schedule) != "layered" or ALGOS[algo] != ALGO_MINSUM:
+        raise ValueError('quant needs schedule="layered" and algo="minsum" (the fixed-point layered min-sum)')
+    return quant
+
+
 def _torch():
     import torch
     if not torch.cuda.is_available():
@@ -139,21 +199,33 @@ def ml_ensemble_decode_dev(n, dv, dc, check_lookup, words, out=None, unsolved=No
 
 # ---------------------------------------------------------------------- soft
 def bp_decode_dev(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False, post=None, hard=None,
-                  its=None, stream=None, want_post=True, want_hard=True, schedule="flooding"):
+                  its=None, stream=None, want_post=True, want_hard=True, schedule="flooding", quant=None):
     """llr: float32 [B, n] device tensor.  Returns (post, hard, its) device tensors.
     schedule: "flooding" (all checks, then all variables) or "layered" (row-serial: every check
     works on the posteriors the checks before it updated, graph.layer_schedule() gives the
-    order; about half the iterations of flooding to converge)."""
+    order; about half the iterations of flooding to converge).
+    quant: a Quant runs the fixed-point layered min-sum (schedule="layered", algo="minsum"; alpha is
+    not read): post is then int8 [B, n], the integer posteriors."""
+    quant = _quant(quant, schedule, algo)
     torch = _torch()
     B = llr.shape[0]
     entry = "ldpc_bp_decode_batch_dev" if _schedule(schedule) == "flooding" else "ldpc_bp_layered_decode_batch_dev"
     assert llr.dtype == torch.float32 and llr.is_contiguous() and llr.shape[1] == graph.n
     if post is None and want_post:
-        post = torch.empty_like(llr)
+        post = torch.empty_like(llr) if quant is None else torch.empty(llr.shape, dtype=torch.int8, device=llr.device)
     if hard is None and want_hard:
         hard = torch.empty(llr.shape, dtype=torch.uint8, device=llr.device)
     if its is None:
         its = torch.empty((B,), dtype=torch.int32, device=llr.device)
+    if quant is not None:
+        import ctypes as ct
+        assert post is None or (post.dtype == torch.int8 and post.is_contiguous() and post.shape == llr.shape)
+        q = quant.native()
+        entry = "ldpc_bp_layered_q_decode_batch_dev"
+        rc = getattr(_native.lib(), entry)(graph.handle(), llr.data_ptr(), B, max_iters, ct.addressof(q),
+                                           int(bool(early_stop)), _ptr(post), _ptr(hard), _ptr(its), _stream(stream))
+        _native.check(rc, entry)
+        return post, hard, its
     rc = getattr(_native.lib(), entry)(graph.handle(), llr.data_ptr(), B, max_iters, ALGOS[algo],
                                        float(alpha), int(bool(early_stop)), _ptr(post), _ptr(hard),
                                        _ptr(its), _stream(stream))
@@ -161,11 +233,12 @@ def bp_decode_dev(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False
     return post, hard, its
 
 
-def bp_decode(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False, schedule="flooding"):
-    """Host form: llr float32 [B, n] numpy.  Returns (post, hard, its) numpy."""
+def bp_decode(graph, llr, max_iters, algo="spa", alpha=1.0, early_stop=False, schedule="flooding", quant=None):
+    """Host form: llr float32 [B, n] numpy.  Returns (post, hard, its) numpy (post int8 with a Quant)."""
+    quant = _quant(quant, schedule, algo)
     torch = _torch()
     t = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(llr), dtype=np.float32)).cuda()
-    post, hard, its = bp_decode_dev(graph, t, max_iters, algo, alpha, early_stop, schedule=schedule)
+    post, hard, its = bp_decode_dev(graph, t, max_iters, algo, alpha, early_stop, schedule=schedule, quant=quant)
     torch.cuda.synchronize()
     return post.cpu().numpy(), hard.cpu().numpy(), its.cpu().numpy()
 

@@ -21,17 +21,28 @@ import time
 import numpy as np
 
 from . import _native
-from .decoder import ALGOS, CHANNELS, _schedule
+from .decoder import ALGOS, CHANNELS, _quant, _schedule
 
 
 def device_executor(mc):
-    """Batch executor backed by ldpc_mc_batch_dev (mc.schedule "layered": ldpc_mc_layered_batch_dev)
-    on the current HIP device."""
+    """Batch executor backed by ldpc_mc_batch_dev (mc.schedule "layered": ldpc_mc_layered_batch_dev,
+    with mc.quant ldpc_mc_layered_q_batch_dev) on the current HIP device."""
     torch = mc.torch
     entry = "ldpc_mc_layered_batch_dev" if mc.schedule == "layered" else "ldpc_mc_batch_dev"
+    if mc.quant is not None:
+        entry = "ldpc_mc_layered_q_batch_dev"
 
     def run(first_cw, B, stop_frame_errors, counters, stream=None):
         s = stream if stream is not None else torch.cuda.current_stream()
+        if mc.quant is not None:
+            import ctypes as ct
+            q = mc.quant.native()
+            rc = getattr(_native.lib(), entry)(mc.graph.handle(), mc.channel, mc.param, mc.seed, int(first_cw),
+                                               int(B), mc.max_iters, ct.addressof(q), int(mc.early_stop),
+                                               mc.expurgation, int(stop_frame_errors), counters.data_ptr(),
+                                               s.cuda_stream)
+            _native.check(rc, entry)
+            return
         rc = getattr(_native.lib(), entry)(mc.graph.handle(), mc.channel, mc.param, mc.seed, int(first_cw),
                                            int(B), mc.max_iters, mc.algo, mc.alpha, int(mc.early_stop),
                                            mc.expurgation, int(stop_frame_errors), counters.data_ptr(),
@@ -98,11 +109,13 @@ class MonteCarlo:
     drops the BP decode and the stop rule then counts ML frame errors.
 
     schedule="layered": the row-serial schedule (decoder.bp_decode_dev) on a fixed code, BSC and
-    BI-AWGN, on one rank or sharded; ensemble runs and the ML modes are flooding-only."""
+    BI-AWGN, on one rank or sharded; ensemble runs and the ML modes are flooding-only.
+    quant=decoder.Quant(...) with schedule="layered" and algo="minsum": the fixed-point layered
+    min-sum (alpha is not read)."""
 
     def __init__(self, graph, channel, param, max_iters, algo="spa", alpha=1.0, early_stop=True,
                  expurgation=-1, seed=0, batch=4096, process_group=None, executor=None, device=None,
-                 optimal=False, message_passing=True, schedule="flooding"):
+                 optimal=False, message_passing=True, schedule="flooding", quant=None):
         import torch
         self.torch = torch
         self.graph = graph
@@ -116,6 +129,7 @@ class MonteCarlo:
         self.param = float(param)
         self.max_iters = int(max_iters)
         self.algo = ALGOS[algo]
+        self.quant = _quant(quant, self.schedule, algo)
         self.alpha = float(alpha)
         self.early_stop = bool(early_stop)
         self.expurgation = int(expurgation)

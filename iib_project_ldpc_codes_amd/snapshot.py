@@ -66,6 +66,8 @@ def config(mc):
            "optimal": bool(mc.optimal), "message_passing": bool(mc.message_passing)}
     if getattr(mc, "schedule", "flooding") == "layered":  # flooding snapshots stay as they always were
         cfg.update({"schedule": "layered", "layer_rule": LAYER_RULE})
+    if getattr(mc, "quant", None) is not None:  # the fixed-point decoder: only then, so every other config is unchanged
+        cfg["quant"] = mc.quant.as_dict()
     return cfg
 
 

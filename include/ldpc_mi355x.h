@@ -193,6 +193,62 @@ int ldpc_mc_layered_batch_dev(const ldpc_graph *g, int channel, float param, uin
                               int64_t stop_frame_errors, int64_t *d_counters, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Fixed-point layered min-sum with compressed check records               */
+/* (csrc/bp_layer_q.hip)                                                    */
+/* ---------------------------------------------------------------------- */
+/*
+ * The layered schedule above as hardware decoders run it: q-bit messages, slightly wider
+ * saturating posteriors, and per check a compressed record (two minima, the index of the
+ * first, the signs) instead of one message per edge.  Parameters: ldpc_quant, with
+ * Q = 2^(msg_bits-1) - 1 and Pmax = 2^(post_bits-1) - 1.
+ *
+ * A parameter set is valid when all of these hold; anything else returns LDPC_EINVAL:
+ *   2 <= msg_bits <= 7
+ *   msg_bits <= post_bits <= 8
+ *   1 <= norm8 <= 8
+ *   0 <= offset <= Q
+ *   scale finite and > 0
+ *
+ * All arithmetic is in integers except the one fp32 product of the channel quantiser.
+ *
+ *   c[v]  = rint_half_even(clamp(llr[v] * scale, -Q, +Q))      (fp32 product, no contraction; NaN -> 0)
+ *   P[v]  = c[v];  R[e] = 0
+ *   iteration t = 1..max_iters, checks in (layer, check id) order of the existing layer schedule,
+ *     slots e_j, variables v_j of the check:
+ *       x_j  = P[v_j] - R[e_j]                                  (not saturated; |x_j| <= Pmax + Q)
+ *       a_j  = min(|x_j|, Q);  s_j = (x_j < 0)                  (0 counts as positive)
+ *       m1 = min a_j, i1 = first index reaching it, m2 = min over j != i1 (degree 1: m2 = Q)
+ *       f(m) = max(((m * norm8) >> 3) - offset, 0)
+ *       |r_j| = f(m2) if j == i1 else f(m1);  r_j negative iff (XOR of all s) ^ s_j, and |r_j| > 0
+ *       P[v_j] = clamp(x_j + r_j, -Pmax, +Pmax);  R[e_j] = r_j
+ *     hard[v] = P[v] < 0;  early_stop: hard satisfies every check -> stop, its = t
+ *
+ * Outputs are post int8[B][n] (the integers P; NULL allowed), hard uint8[B][n] (NULL allowed)
+ * and its int32[B].  max_iters = 0 returns c and c < 0, with its = 0.  B = 0, the NULL rules
+ * and streams behave as ldpc_bp_layered_decode_batch_dev.  A graph without a layer schedule
+ * returns LDPC_EUNSUP.  A graph whose block does not fit LDS (ldpc_debug_layer_q_plan) returns
+ * LDPC_EUNSUP.
+ *
+ * R is written per edge above only to define the result.  The record (f(m1), f(m2), i1, sign
+ * bits of r) reproduces it exactly.  The kernel stores the record, never R.
+ */
+typedef struct ldpc_quant {
+    float scale;
+    int32_t msg_bits, post_bits, norm8, offset;
+} ldpc_quant;
+int ldpc_bp_layered_q_decode_batch_dev(const ldpc_graph *g, const float *d_llr, int B, int max_iters,
+                                       const ldpc_quant *q, int early_stop, int8_t *d_post, uint8_t *d_hard,
+                                       int32_t *d_its, void *stream);
+/*
+ * ldpc_mc_layered_batch_dev on the fixed-point decoder (the device channel's LLR goes through the
+ * quantiser): curve[0] = c < 0, curve[t] = P < 0 after iteration t, repeated after a stop;
+ * counters, expurgation and the sequential stop rule exactly as there.  LDPC_CH_BEC: LDPC_EINVAL.
+ */
+int ldpc_mc_layered_q_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t seed, uint64_t first_cw,
+                                int B, int max_iters, const ldpc_quant *q, int early_stop, int expurgation,
+                                int64_t stop_frame_errors, int64_t *d_counters, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* Whole Monte-Carlo run over several devices of one process */
 /* ---------------------------------------------------------------------- */
 /*
@@ -438,6 +494,20 @@ const char *ldpc_layer_rule(void);
 int ldpc_debug_layer_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
                           const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
                           int64_t *out, char *names);
+
+/*
+ * Host-only: the launch plans of `count` fixed-point layered calls on one CSR graph (csrc/bp_plan.cpp
+ * bp_layer_q_plan); calls / out / names as ldpc_debug_layer_plan (algo is not read), names
+ * bp_layer_q_kernel<8|16|32>, and column 4 of a row (lds_slots elsewhere) holds the number of
+ * workgroups one CU holds at once.  A call whose block does not fit LDS gets the row of no plan
+ * (name "none"): the decode entries return LDPC_EUNSUP for it.  LDPC_EUNSUP when the graph has no
+ * layer schedule.
+ */
+int ldpc_debug_layer_q_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                            const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
+                            int64_t *out, char *names);
+/* Host-only: LDPC_OK for a valid parameter set (the rules above), else LDPC_EINVAL. */
+int ldpc_quant_check(const ldpc_quant *q);
 
 /*
  * Host-only: the launch plans of `count` BEC erasure-decoding calls on a graph of n variables

@@ -9,6 +9,8 @@
         early stop, no expurgation unless --expurgation is given)
 --schedule layered (cfg3, cfg4): the row-serial schedule of hardware decoders on the fixed code
 (decoder.bp_decode_dev; the ensemble has no layered form).
+--quant bits,post_bits,scale,norm8,offset (cfg3 with --schedule layered): the fixed-point layered
+min-sum (decoder.Quant) -- what frame error rate a q-bit hardware decoder reaches.
 One process per GPU: `--gpus N` starts the N ranks itself (decided before any HIP call, refused
 when fewer than N GPUs are visible -- iib_project_ldpc_codes_amd/launch.py, the same plan as
 bench.py), or runs as a rank of an external torchrun; trials shard by index, counters are
@@ -19,6 +21,7 @@ parallel_simulator.py:198), --trials, or --seconds.
   python scripts/fer_sweep.py cfg4 --gpus 8 --seconds 300
   python scripts/fer_sweep.py ens --channel bsc --algo minsum --points 0.07,0.065
   python scripts/fer_sweep.py cfg3 --schedule layered --points 0.07
+  python scripts/fer_sweep.py cfg3 --schedule layered --quant 5,7,2.0,6,0 --points 0.07
 """
 import argparse
 import json
@@ -35,6 +38,18 @@ from iib_project_ldpc_codes_amd import de, ensembles, snapshot  # noqa: E402
 from iib_project_ldpc_codes_amd.launch import launch_plan, spawn_ranks  # noqa: E402
 from iib_project_ldpc_codes_amd.graph import TannerGraph  # noqa: E402
 from iib_project_ldpc_codes_amd.montecarlo import MonteCarlo  # noqa: E402
+
+
+def parse_quant(text):
+    """bits,post_bits,scale,norm8,offset -> decoder.Quant"""
+    from iib_project_ldpc_codes_amd.decoder import Quant
+    f = text.split(",")
+    if len(f) != 5:
+        raise argparse.ArgumentTypeError("--quant takes bits,post_bits,scale,norm8,offset")
+    try:
+        return Quant(int(f[0]), int(f[1]), float(f[2]), int(f[3]), int(f[4]))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def parse(argv=None):
@@ -56,6 +71,8 @@ def parse(argv=None):
                     help="ens on bsc / awgn: the decoder (default minsum on bsc, spa on awgn)")
     ap.add_argument("--schedule", choices=["flooding", "layered"], default="flooding",
                     help="cfg3 / cfg4: the decoding schedule (layered: row-serial, about half the iterations)")
+    ap.add_argument("--quant", type=parse_quant, default=None, metavar="BITS,POST_BITS,SCALE,NORM8,OFFSET",
+                    help="cfg3 with --schedule layered: the fixed-point layered min-sum (decoder.Quant)")
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks, one process per GPU (default: torchrun's WORLD_SIZE, else 1); "
                          "without WORLD_SIZE the sweep starts them itself")
@@ -68,6 +85,8 @@ def parse(argv=None):
         args.expurgation = 3 if args.channel == "bec" else -1
     if args.schedule == "layered" and args.config == "ens":
         ap.error("--schedule layered needs a fixed code (cfg3, cfg4): no host-built schedule per sampled graph")
+    if args.quant is not None and (args.schedule != "layered" or args.config != "cfg3"):
+        ap.error("--quant needs cfg3 (min-sum) with --schedule layered")
     return args
 
 
@@ -114,11 +133,14 @@ def main(argv=None):
                                      expurgation=args.expurgation, seed=args.seed, batch=batch)
         else:
             mc = MonteCarlo(g, channel, p, iters, algo=algo, alpha=alpha, early_stop=True, seed=args.seed,
-                            batch=batch, schedule=args.schedule)
+                            batch=batch, schedule=args.schedule, quant=args.quant)
         ck = None
         if args.checkpoint_dir:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
             tag = "" if args.schedule == "flooding" else "_" + args.schedule  # flooding keeps its file names
+            if args.quant is not None:
+                q = args.quant
+                tag += "_q%d-%d-%g-%d-%d" % (q.bits, q.post_bits, q.scale, q.norm8, q.offset)
             ck = os.path.join(args.checkpoint_dir, f"{args.config}{tag}_p={p}_seed={args.seed}_B={batch}.json")
             if os.path.exists(ck):
                 mc.restore(snapshot.load(ck))
@@ -136,6 +158,8 @@ def main(argv=None):
                    "seconds": el, "codewords_per_s": (res["num_tests"] - trials0) / el}
             if args.schedule != "flooding":
                 out["schedule"] = args.schedule
+            if args.quant is not None:
+                out["quant"] = args.quant.as_dict()
             if channel == "awgn":
                 out["ebn0_db"] = float(de.sigma_to_ebn0_db(p, rate))
             print(json.dumps(out), flush=True)
