@@ -132,6 +132,10 @@ int ldpc_bp_decode_batch_dev(const ldpc_graph *g, const float *d_llr, int B, int
  * Channel outputs for the all-zero codeword (parallel_simulator.py:222) of
  * codewords first_cw .. first_cw+B-1, Philox4x32-10 (rocRAND) keyed by seed:
  * BEC writes uint8 0/2 into d_out, BSC / AWGN write float LLRs.
+ * Here and in every Monte-Carlo entry below, seed and the trial index
+ * first_cw + b are used in full 64-bit width (the low and high words of each
+ * are Philox key and counter words): trial t is the same whatever batch it is
+ * drawn in, on either side of 2^32 (tests/test_gpu_index64.py).
  */
 int ldpc_channel_dev(int channel, float param, uint64_t seed, uint64_t first_cw, int n, int B,
                      void *d_out, void *stream);
@@ -293,7 +297,9 @@ int ldpc_mc_run_csr(const int32_t *check_ptr, const int32_t *check_var, const in
  * reference's edge-list format: check_lookup int32[G][n*dv] (variables of check
  * c at [c*dc, c*dc+dc)), variable_lookup int32[G][n*dv] (checks of each variable,
  * ascending).  Counter-based (Philox, key = seed): graph g is the same whatever
- * G / first_graph batch it is drawn in.  attempts int32[G] (may be NULL): number
+ * G / first_graph batch it is drawn in; seed and the graph index first_graph + g
+ * are used in full 64-bit width, here and in the CSR form below (an ensemble
+ * trial t draws graph t).  attempts int32[G] (may be NULL): number
  * of permutations drawn for each graph.  The dense parity-check matrix is never
  * built.
  */

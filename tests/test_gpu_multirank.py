@@ -74,6 +74,57 @@ def test_two_ranks_equal_sequential(case):
         np.testing.assert_array_equal(np.array(counters), want, err_msg=f"rank {rank}")
 
 
+def _restored(mc, base):
+    """mc continuing at trial `base` with empty counters (collective: every rank calls it)."""
+    snap = mc.snapshot()
+    snap["trial_ranges"] = [[base, base]]
+    mc.restore(snap)
+    return mc
+
+
+def _worker_restored(rank, world, port, case, base, num_tests, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        mc = _restored(_mc(case), base)
+        res = mc.run(num_tests=num_tests, stop_frame_errors=0)
+        q.put((rank, res["raw_counters"].tolist(), mc.rounds, mc.next_trial()))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_two_ranks_cross_trial_2_32():
+    """Both runs restored to trial 2^32 - 384: six batches of 256 in one process, three rounds on
+    two ranks (rank 1's first batch holds trial 2^32); the counters must be identical.  The kernel
+    of this case is held to the oracle across 2^32 by tests/test_gpu_index64.py."""
+    import torch
+    case, world = "bsc_minsum", 2
+    batch = CASES[case]["batch"]
+    base, num_tests = 2 ** 32 - batch - batch // 2, 6 * batch
+    ref = _restored(_mc(case), base)
+    want = ref.run(num_tests=num_tests, stop_frame_errors=0)["raw_counters"]
+    torch.cuda.synchronize()
+    assert ref.rounds == 6 and ref.next_trial() == base + num_tests == 2 ** 32 + 1152
+    assert want[0] == num_tests and 0 < want[1] < num_tests
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_restored, args=(r, world, port, case, base, num_tests, q))
+             for r in range(world)]
+    for p in procs:
+        p.start()
+    out = [q.get(timeout=100) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=30)
+        assert p.exitcode == 0
+    for rank, counters, rounds, nxt in out:
+        np.testing.assert_array_equal(np.array(counters), want, err_msg=f"rank {rank}")
+        assert rounds == 3 and nxt == base + num_tests
+
+
 # ------------------------------------------- ldpc_mc_run (one process, RCCL over devices)
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_mc_run_one_device_equals_montecarlo(case):
