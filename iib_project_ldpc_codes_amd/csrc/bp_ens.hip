@@ -1,5 +1,5 @@
 // bp_ens_kernel: soft decoding over the random (dv, dc) ensemble -- codeword b on its own graph,
-// rows b of the sampler's two lists -- and its launchers.
+// rows b of the sampler's two lists -- and its launch (EnsFamily, ldpc_internal.hpp).
 #include "kernel_args.hpp"
 
 // ---------------------------------------------------------------------------
@@ -24,10 +24,10 @@
 #include "bp_flood.hpp"
 
 namespace ldpc {
-namespace {
 
-EnsArgs ens_args(int n, int dv, int dc, const int32_t *chk, const int32_t *var, int B, int iters, float alpha) {
-    EnsArgs a{};
+hipError_t EnsFamily::launch(const BpPlan &p, const SoftCall &c, float *scratch, hipStream_t s) const {
+    if (p.path == BpPath::None) return hipErrorNotSupported;
+    EnsArgs a = call_args<EnsArgs>(c);
     a.chk = chk;
     a.var = var;
     a.n = n;
@@ -35,51 +35,8 @@ EnsArgs ens_args(int n, int dv, int dc, const int32_t *chk, const int32_t *var, 
     a.dc = dc;
     a.E = n * dv;
     a.m = a.E / dc;
-    a.B = B;
-    a.max_iters = iters;
-    a.alpha = alpha;
-    return a;
-}
-
-hipError_t launch_ens(EnsArgs a, float *d_scratch, size_t scratch_bytes, int algo, bool et, bool mc, hipStream_t s) {
-    const BpPlan p = bp_ens_plan(a.n, a.dv, a.dc, a.B, a.max_iters, algo, et, mc, a.post != nullptr, device_cus());
-    if (p.path == BpPath::None) return hipErrorNotSupported;
-    // a caller that sized the buffer by another rule than bp_ens_plan's fails loudly
-    if (p.scratch > (d_scratch ? scratch_bytes : 0)) return hipErrorInvalidValue;
-    a.scratch = d_scratch;
-    return launch_flood(p, a, algo, et, mc, s, BpPath::Ens8, hipErrorNotSupported);
-}
-
-}  // namespace
-
-size_t ens_scratch_bytes(int n, int dv, int dc, int B, int iters, int algo, bool early_stop, bool mc, bool want_post) {
-    return bp_ens_plan(n, dv, dc, B, iters, algo, early_stop, mc, want_post, device_cus()).scratch;
-}
-
-hipError_t launch_ens_decode(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
-                             const float *d_llr, int B, int max_iters, int algo, float alpha, int early_stop,
-                             float *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream, float *d_scratch,
-                             size_t scratch_bytes) {
-    if (B <= 0) return hipSuccess;
-    EnsArgs a = ens_args(n, dv, dc, check_lookup, variable_lookup, B, max_iters, alpha);
-    a.llr = d_llr;
-    a.post = d_post;
-    a.hard = d_hard;
-    a.its = d_its;
-    return launch_ens(a, d_scratch, scratch_bytes, algo, early_stop != 0, false, stream);
-}
-
-hipError_t launch_mc_ens(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
-                         int channel, float p, float p2, uint64_t seed, uint64_t first_cw, int B, int max_iters,
-                         int algo, float alpha, int early_stop, int32_t *trial, int32_t *trial_its,
-                         hipStream_t stream, float *d_scratch, size_t scratch_bytes) {
-    if (B <= 0) return hipSuccess;
-    EnsArgs a = ens_args(n, dv, dc, check_lookup, variable_lookup, B, max_iters, alpha);
-    a.ch = make_chan(channel, p, p2, seed);
-    a.first_cw = first_cw;
-    a.trial = trial;
-    a.its = trial_its;
-    return launch_ens(a, d_scratch, scratch_bytes, algo, early_stop != 0, true, stream);
+    a.scratch = scratch;
+    return launch_flood(p, a, c.algo, c.early_stop, c.mc, s, BpPath::Ens8, hipErrorNotSupported);
 }
 
 }  // namespace ldpc

@@ -52,19 +52,117 @@ using OwnedGraph = std::unique_ptr<ldpc_graph, void (*)(ldpc_graph *)>;
         if (!(ptrs)) return LDPC_EHIP; \
     } while (0)
 
-// The workspace's scratch buffer grown to `bytes` (nullptr: none needed); false: allocation failed
-static bool get_scratch(Workspace &ws, size_t bytes, float *&scratch) {
-    scratch = bytes ? ws.scratch.get<float>((bytes + 3) / 4) : nullptr;
-    return !bytes || scratch;
+// The rows of the ldpc_debug_*_plan entries.  calls[i] = {B, iters, algo, early_stop, mc,
+// want_post}, planned by `plan` with those six; out + 9 i = {path, threads, grid, LDS bytes, col4
+// (lds_slots; bp_layer_q_plan's: wg_per_cu), persistent, slab bytes, counter offset (-1: none),
+// scratch bytes}; names + 64 i: the kernel's display name.  no_plan: the error (LDPC_EUNSUP, after
+// every row is filled) when a call has no kernel; nullptr: such a row is an answer like any other.
+template <typename Plan>
+static int write_plans(int count, const int32_t *calls, int64_t *out, char *names, int BpPlan::*col4,
+                       const char *no_plan, Plan plan) {
+    bool none = false;
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 6 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        const BpPlan p = plan(c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0);
+        int64_t *o = out + 9 * (size_t)i;
+        o[0] = (int64_t)p.path; o[1] = p.threads; o[2] = p.grid; o[3] = (int64_t)p.lds; o[4] = p.*col4;
+        o[5] = p.persistent; o[6] = (int64_t)p.slab; o[7] = p.counter; o[8] = (int64_t)p.scratch;
+        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+        none |= p.path == BpPath::None;
+    }
+    if (none && no_plan) {
+        set_error(no_plan);
+        return LDPC_EUNSUP;
+    }
+    return LDPC_OK;
 }
 
-// Row i of the debug plans: out + 9 i = {path, threads, grid, LDS bytes, lds_slots, persistent,
-// slab bytes, counter offset (-1: none), scratch bytes}; names + 64 i: the kernel's display name
-static void write_plan(const BpPlan &p, int i, int64_t *out, char *names) {
-    int64_t *o = out + 9 * (size_t)i;
-    o[0] = (int64_t)p.path; o[1] = p.threads; o[2] = p.grid; o[3] = (int64_t)p.lds; o[4] = p.lds_slots;
-    o[5] = p.persistent; o[6] = (int64_t)p.slab; o[7] = p.counter; o[8] = (int64_t)p.scratch;
-    snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+static const char *const kNoSchedule =
+    "graph has no layer schedule (needs consistent lists, check degrees 1..32, no check holding a variable twice)";
+
+// The three plan entries of a fixed code: its host layouts, then write_plans' rows of `plan` (bp_plan,
+// bp_layer_plan or bp_layer_q_plan).  need_schedule: LDPC_EUNSUP up front for a graph without one.
+static int graph_plans(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                       const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
+                       char *names, decltype(bp_plan) *plan, bool need_schedule, int BpPlan::*col4) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
+    HostGraph h;
+    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
+    GraphShape g;
+    HostLayouts L;
+    host_layouts(h, g, L, true, layout_options());
+    if (need_schedule && g.lay_L <= 0) {
+        set_error(kNoSchedule);
+        return LDPC_EUNSUP;
+    }
+    return write_plans(count, calls, out, names, col4, nullptr,
+                       [&](int B, int iters, int algo, bool et, bool mc, bool want_post) {
+                           return plan(g, B, iters, algo, et, mc, want_post, cus);
+                       });
+}
+
+// ---- the soft decoders' path from an entry to a launch: a SoftCall and a family (ldpc_internal.hpp)
+// The call of a decode (post nullptr: no posteriors asked for, early stop may take the hard-decision path)
+static SoftCall decode_call(int B, int max_iters, int algo, float alpha, int early_stop, const float *llr, void *post,
+                            uint8_t *hard, int32_t *its) {
+    SoftCall c{B, max_iters, algo, alpha, early_stop != 0, false};
+    c.llr = llr, c.post = post, c.hard = hard, c.its = its;
+    return c;
+}
+// The call of a fused Monte-Carlo batch (mc_entry gives it trial and its)
+static SoftCall mc_call(int B, int max_iters, int algo, float alpha, int early_stop, const ChanArgs &ch,
+                        uint64_t first_cw) {
+    SoftCall c{B, max_iters, algo, alpha, early_stop != 0, true};
+    c.ch = ch, c.first_cw = first_cw;
+    return c;
+}
+
+// The one step every soft call goes through, its workspace locked: plan once, take the plan's
+// scratch from the workspace -- the one place a buffer shorter than the plan's is refused -- and
+// launch from that same plan.  B > 0.
+template <typename Family>
+static int soft_launch(Workspace &ws, const Family &f, const SoftCall &c, hipStream_t s) {
+    const BpPlan p = f.plan(c, device_cus());
+    float *scratch = p.scratch ? ws.scratch.get<float>((p.scratch + 3) / 4) : nullptr;
+    LDPC_ALLOCATED(scratch || !p.scratch);
+    if (p.scratch > (scratch ? ws.scratch.cap : 0)) LDPC_HIP(hipErrorInvalidValue);
+    LDPC_HIP(f.launch(p, c, scratch, s));
+    return LDPC_OK;
+}
+
+// The device decode entries' driver: g_mu, then the workspace's lock, both held across the
+// (asynchronous) launch (workspace.hpp).  Arguments validated by the entry; B > 0.
+template <typename Family>
+static int decode_entry(const Family &f, const SoftCall &c, void *stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Workspace &ws = workspace(stream);
+    std::lock_guard<std::mutex> wl(ws.mu);
+    return soft_launch(ws, f, c, static_cast<hipStream_t>(stream));
+}
+
+// The fused Monte-Carlo entries' driver: this (device, stream)'s workspace lock only, so devices
+// launch in parallel; the per-trial curves [B][max_iters + 1] and iteration counts [B] that
+// decode(ws, c, s) has the batch's kernels fill -- after sampling the trials' graphs, for an
+// ensemble -- then the reducer with its cutoff.  Arguments validated by the entry; B > 0.
+template <typename Decode>
+static int mc_entry(SoftCall c, int expurgation, int64_t stop_frame_errors, int64_t *d_counters, void *stream,
+                    Decode decode) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Workspace &ws = workspace(stream);
+    std::lock_guard<std::mutex> wl(ws.mu);
+    c.trial = ws.trial.get<int32_t>((size_t)c.B * (c.max_iters + 1));
+    c.its = ws.its.get<int32_t>(c.B);
+    int32_t *cut = ws.cutoff.get<int32_t>(4);
+    LDPC_ALLOCATED(c.trial && c.its && cut);
+    LDPC_TRY(decode(ws, c, s));
+    LDPC_HIP(launch_mc_reduce(c.trial, c.its, c.B, c.max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
+    return LDPC_OK;
+}
+// mc_entry's `decode` of a fixed code's family: soft_launch alone
+template <typename Family>
+static auto soft_decode(const Family &f) {
+    return [f](Workspace &ws, const SoftCall &c, hipStream_t s) { return soft_launch(ws, f, c, s); };
 }
 
 extern "C" {
@@ -224,23 +322,12 @@ int ldpc_debug_loc_variant(const int32_t *check_ptr, const int32_t *check_var, c
 }
 
 // The launch plans (bp_plan) of `count` soft-decoding calls on one graph, from the host layouts
-// alone.  calls[i] = {B, iters, algo, early_stop, mc, want_post}; out / names: write_plan's rows.
+// alone; calls / out / names: write_plans'.
 int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
                        const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
                        char *names) {
-    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
-    HostGraph h;
-    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
-    GraphShape g;
-    HostLayouts L;
-    host_layouts(h, g, L, true, layout_options());
-    for (int i = 0; i < count; ++i) {
-        const int32_t *c = calls + 6 * (size_t)i;
-        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
-        const BpPlan p = bp_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus);
-        write_plan(p, i, out, names);
-    }
-    return LDPC_OK;
+    return graph_plans(check_ptr, check_var, var_ptr, var_slot, n, m, count, calls, cus, out, names, bp_plan, false,
+                       &BpPlan::lds_slots);
 }
 
 // The launch plans (bec_plan) of `count` BEC calls on an (n, m) graph of check degree dc (0:
@@ -342,19 +429,6 @@ int message_passing(int *Mvc, int iterations, int *variable_to_check_list, int *
 }
 
 // --------------------------- soft ------------------------------------------
-// The soft decode of both forms: scratch from the (locked) workspace, then the launch.  B > 0.
-static int bp_decode_locked(Workspace &ws, const ldpc_graph &g, const float *d_llr, int B, int max_iters, int algo,
-                            float alpha, int early_stop, float *d_post, uint8_t *d_hard, int32_t *d_its,
-                            hipStream_t s) {
-    const size_t sb = bp_scratch_bytes(g, B, max_iters, algo, early_stop != 0, false, d_post != nullptr);
-    float *scratch;
-    LDPC_ALLOCATED(get_scratch(ws, sb, scratch));
-    // no posteriors asked for: early stop may take the hard-decision path (bp_loc_kernel)
-    LDPC_HIP(launch_bp_decode(g, d_llr, B, max_iters, algo, alpha, early_stop, d_post, d_hard, d_its, s, scratch,
-                              ws.scratch.cap));
-    return LDPC_OK;
-}
-
 int ldpc_bp_decode_batch_dev(const ldpc_graph *g, const float *d_llr, int B, int max_iters, int algo, float alpha,
                              int early_stop, float *d_post, uint8_t *d_hard, int32_t *d_its, void *stream) {
     LDPC_REQUIRE(g && (B == 0 || d_llr) && B >= 0 && max_iters >= 0, "bad soft batch arguments");
@@ -366,14 +440,13 @@ int ldpc_bp_decode_batch_dev(const ldpc_graph *g, const float *d_llr, int B, int
         return LDPC_EUNSUP;
     }
     if (B == 0) return LDPC_OK;
-    std::lock_guard<std::mutex> lk(g_mu);
-    Workspace &ws = workspace(stream);
-    std::lock_guard<std::mutex> wl(ws.mu);
-    return bp_decode_locked(ws, *g, d_llr, B, max_iters, algo, alpha, early_stop, d_post, d_hard, d_its,
-                            static_cast<hipStream_t>(stream));
+    const SoftCall c = decode_call(B, max_iters, algo, alpha, early_stop, d_llr, d_post, d_hard, d_its);
+    return decode_entry(FloodFamily{*g}, c, stream);
 }
 
-// Inconsistent lists or a graph no kernel covers: the launcher refuses them (LDPC_EHIP).
+// Inconsistent lists or a graph no kernel covers: FloodFamily::launch refuses them (LDPC_EHIP).  The
+// staging buffers live in the workspace, so this form holds decode_entry's two locks itself, from
+// the staging to the copies back, and goes through soft_launch under them.
 int ldpc_bp_decode_batch(const int32_t *variable_to_check_list, const int32_t *check_to_variable_list, int n, int k,
                          int dv, int dc, const float *llr, int B, int max_iters, int algo, float alpha,
                          int early_stop, float *post, uint8_t *hard, int32_t *its) {
@@ -392,7 +465,8 @@ int ldpc_bp_decode_batch(const int32_t *variable_to_check_list, const int32_t *c
     int32_t *di = ws.itsb.get<int32_t>((size_t)B + 1);
     LDPC_ALLOCATED(dl && dp && dh && di);
     LDPC_HIP(hipMemcpy(dl, llr, nb * 4, hipMemcpyHostToDevice));
-    LDPC_TRY(bp_decode_locked(ws, *g, dl, B, max_iters, algo, alpha, early_stop, post ? dp : nullptr, dh, di, nullptr));
+    const SoftCall c = decode_call(B, max_iters, algo, alpha, early_stop, dl, post ? dp : nullptr, dh, di);
+    LDPC_TRY(soft_launch(ws, FloodFamily{*g}, c, nullptr));
     LDPC_HIP(hipDeviceSynchronize());
     if (post) LDPC_HIP(hipMemcpy(post, dp, nb * 4, hipMemcpyDeviceToHost));
     if (hard) LDPC_HIP(hipMemcpy(hard, dh, nb, hipMemcpyDeviceToHost));
@@ -438,25 +512,17 @@ int ldpc_mc_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t se
         LDPC_REQUIRE(g->consistent, "soft decoding needs consistent edge lists");
     }
     if (B == 0) return LDPC_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only: devices launch in parallel
-    std::lock_guard<std::mutex> wl(ws.mu);
-    // per-trial curves [B][max_iters + 1] and iteration counts [B], then the reducer's cutoff
-    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
-    int32_t *cut = ws.cutoff.get<int32_t>(4);
-    const size_t sb = channel != LDPC_CH_BEC ? bp_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, true, false) : 0;
-    float *scratch;
-    LDPC_ALLOCATED(trial && its && cut && get_scratch(ws, sb, scratch));
-    LDPC_HIP(launch_mc_decode(*g, channel, p, p2, seed, first_cw, B, max_iters, algo, alpha, early_stop, trial, its,
-                              s, scratch, sb ? ws.scratch.cap : 0));
-    LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
-    return LDPC_OK;
+    const SoftCall c = mc_call(B, max_iters, algo, alpha, early_stop, make_chan(channel, p, p2, seed), first_cw);
+    if (channel != LDPC_CH_BEC)
+        return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream, soft_decode(FloodFamily{*g}));
+    return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream,
+                    [&](Workspace &, const SoftCall &mc, hipStream_t s) {  // exact erasure decoding (bec.hip)
+                        LDPC_HIP(launch_mc_bec(*g, p, p2, seed, first_cw, B, max_iters, mc.trial, mc.its, s));
+                        return (int)LDPC_OK;
+                    });
 }
 
 // --------------------------- layered schedule ------------------------------
-static const char *const kNoSchedule =
-    "graph has no layer schedule (needs consistent lists, check degrees 1..32, no check holding a variable twice)";
-
 // The argument checks the two layered entries share; LDPC_EUNSUP for a graph without a schedule
 static int layered_check(const ldpc_graph *g, int algo) {
     LDPC_REQUIRE(algo == LDPC_ALGO_SPA || algo == LDPC_ALGO_MINSUM, "algo must be LDPC_ALGO_SPA or LDPC_ALGO_MINSUM");
@@ -475,15 +541,8 @@ int ldpc_bp_layered_decode_batch_dev(const ldpc_graph *g, const float *d_llr, in
     LDPC_REQUIRE(g && (B == 0 || d_llr) && B >= 0 && max_iters >= 0, "bad soft batch arguments");
     LDPC_TRY(layered_check(g, algo));
     if (B == 0) return LDPC_OK;
-    std::lock_guard<std::mutex> lk(g_mu);
-    Workspace &ws = workspace(stream);
-    std::lock_guard<std::mutex> wl(ws.mu);
-    const size_t sb = layer_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, false, d_post != nullptr);
-    float *scratch;
-    LDPC_ALLOCATED(get_scratch(ws, sb, scratch));
-    LDPC_HIP(launch_layer_decode(*g, d_llr, B, max_iters, algo, alpha, early_stop, d_post, d_hard, d_its,
-                                 static_cast<hipStream_t>(stream), scratch, sb ? ws.scratch.cap : 0));
-    return LDPC_OK;
+    const SoftCall c = decode_call(B, max_iters, algo, alpha, early_stop, d_llr, d_post, d_hard, d_its);
+    return decode_entry(LayerFamily{*g}, c, stream);
 }
 
 int ldpc_mc_layered_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t seed, uint64_t first_cw, int B,
@@ -495,18 +554,8 @@ int ldpc_mc_layered_batch_dev(const ldpc_graph *g, int channel, float param, uin
     LDPC_TRY(channel_params(channel, param, &p, &p2));
     LDPC_TRY(layered_check(g, algo));
     if (B == 0) return LDPC_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only: devices launch in parallel
-    std::lock_guard<std::mutex> wl(ws.mu);
-    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
-    int32_t *cut = ws.cutoff.get<int32_t>(4);
-    const size_t sb = layer_scratch_bytes(*g, B, max_iters, algo, early_stop != 0, true, false);
-    float *scratch;
-    LDPC_ALLOCATED(trial && its && cut && get_scratch(ws, sb, scratch));
-    LDPC_HIP(launch_mc_layer(*g, channel, p, p2, seed, first_cw, B, max_iters, algo, alpha, early_stop, trial, its, s,
-                             scratch, sb ? ws.scratch.cap : 0));
-    LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
-    return LDPC_OK;
+    const SoftCall c = mc_call(B, max_iters, algo, alpha, early_stop, make_chan(channel, p, p2, seed), first_cw);
+    return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream, soft_decode(LayerFamily{*g}));
 }
 
 const char *ldpc_layer_rule(void) { return kLayerRule; }
@@ -529,22 +578,8 @@ int ldpc_debug_layer_schedule(const int32_t *check_ptr, const int32_t *check_var
 int ldpc_debug_layer_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
                           const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
                           char *names) {
-    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
-    HostGraph h;
-    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
-    GraphShape g;
-    HostLayouts L;
-    host_layouts(h, g, L, true, layout_options());
-    if (g.lay_L <= 0) {
-        set_error(kNoSchedule);
-        return LDPC_EUNSUP;
-    }
-    for (int i = 0; i < count; ++i) {
-        const int32_t *c = calls + 6 * (size_t)i;
-        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
-        write_plan(bp_layer_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus), i, out, names);
-    }
-    return LDPC_OK;
+    return graph_plans(check_ptr, check_var, var_ptr, var_slot, n, m, count, calls, cus, out, names, bp_layer_plan,
+                       true, &BpPlan::lds_slots);
 }
 
 // --------------------------- fixed-point layered min-sum -------------------
@@ -576,9 +611,8 @@ int ldpc_bp_layered_q_decode_batch_dev(const ldpc_graph *g, const float *d_llr, 
     LDPC_REQUIRE(g && (B == 0 || d_llr) && B >= 0 && max_iters >= 0, "bad soft batch arguments");
     LDPC_TRY(layered_q_check(g, q, B, max_iters, false));
     if (B == 0) return LDPC_OK;
-    LDPC_HIP(launch_layer_q_decode(*g, d_llr, B, max_iters, *q, early_stop, d_post, d_hard, d_its,
-                                   static_cast<hipStream_t>(stream)));
-    return LDPC_OK;
+    const SoftCall c = decode_call(B, max_iters, LDPC_ALGO_MINSUM, 1.0f, early_stop, d_llr, d_post, d_hard, d_its);
+    return decode_entry(LayerQFamily{*g, *q}, c, stream);
 }
 
 int ldpc_mc_layered_q_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t seed, uint64_t first_cw,
@@ -590,38 +624,16 @@ int ldpc_mc_layered_q_batch_dev(const ldpc_graph *g, int channel, float param, u
     LDPC_TRY(channel_params(channel, param, &p, &p2));
     LDPC_TRY(layered_q_check(g, q, B, max_iters, true));
     if (B == 0) return LDPC_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only: devices launch in parallel
-    std::lock_guard<std::mutex> wl(ws.mu);
-    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
-    int32_t *cut = ws.cutoff.get<int32_t>(4);
-    LDPC_ALLOCATED(trial && its && cut);
-    LDPC_HIP(launch_mc_layer_q(*g, channel, p, p2, seed, first_cw, B, max_iters, *q, early_stop, trial, its, s));
-    LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
-    return LDPC_OK;
+    const SoftCall c =
+        mc_call(B, max_iters, LDPC_ALGO_MINSUM, 1.0f, early_stop, make_chan(channel, p, p2, seed), first_cw);
+    return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream, soft_decode(LayerQFamily{*g, *q}));
 }
 
 int ldpc_debug_layer_q_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
                             const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
                             char *names) {
-    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
-    HostGraph h;
-    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
-    GraphShape g;
-    HostLayouts L;
-    host_layouts(h, g, L, true, layout_options());
-    if (g.lay_L <= 0) {
-        set_error(kNoSchedule);
-        return LDPC_EUNSUP;
-    }
-    for (int i = 0; i < count; ++i) {
-        const int32_t *c = calls + 6 * (size_t)i;
-        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
-        const BpPlan p = bp_layer_q_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus);
-        write_plan(p, i, out, names);
-        out[9 * (size_t)i + 4] = p.wg_per_cu;
-    }
-    return LDPC_OK;
+    return graph_plans(check_ptr, check_var, var_ptr, var_slot, n, m, count, calls, cus, out, names, bp_layer_q_plan,
+                       true, &BpPlan::wg_per_cu);
 }
 
 // --------------------------- random graphs / ensemble MC -------------------
@@ -795,16 +807,15 @@ int ldpc_mc_ensemble_batch_dev(int n, int dv, int dc, int channel, float param, 
     LDPC_TRY(channel_params(channel, param, &p, &p2));
     LDPC_TRY(require_device());
     if (B == 0) return LDPC_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only: devices launch in parallel
-    std::lock_guard<std::mutex> wl(ws.mu);
-    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
-    int32_t *cut = ws.cutoff.get<int32_t>(4), *chk = nullptr, *var = nullptr;
-    LDPC_ALLOCATED(trial && its && cut);
-    LDPC_TRY(sample_regular_locked(ws, n, dv, dc, seed, first_cw, B, chk, var, nullptr, s));
-    LDPC_HIP(launch_mc_bec_ensemble(n, dv, dc, chk, var, p, seed, first_cw, B, max_iters, trial, its, s));
-    LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
-    return LDPC_OK;
+    const SoftCall c = mc_call(B, max_iters, 0, 1.0f, 0, make_chan(channel, p, p2, seed), first_cw);
+    return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream,
+                    [&](Workspace &ws, const SoftCall &mc, hipStream_t s) {
+                        int32_t *chk = nullptr, *var = nullptr;
+                        LDPC_TRY(sample_regular_locked(ws, n, dv, dc, seed, first_cw, B, chk, var, nullptr, s));
+                        LDPC_HIP(launch_mc_bec_ensemble(n, dv, dc, chk, var, p, seed, first_cw, B, max_iters, mc.trial,
+                                                        mc.its, s));
+                        return (int)LDPC_OK;
+                    });
 }
 
 // --------------------------- ensemble soft decoding / MC -------------------
@@ -821,24 +832,16 @@ static int ens_soft_check(int n, int dv, int dc, int algo) {
 }
 
 // The launch plans (bp_ens_plan) of `count` ensemble soft-decoding calls on the (n, dv, dc)
-// shape, host only; calls / out / names as ldpc_debug_bp_plan.  LDPC_EUNSUP (after filling
-// out and names) when a call has no kernel.
+// shape, host only; calls / out / names: write_plans'.  LDPC_EUNSUP (after filling out and names)
+// when a call has no kernel.
 int ldpc_debug_ens_plan(int n, int dv, int dc, int count, const int32_t *calls, int cus, int64_t *out, char *names) {
     LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
     LDPC_TRY(check_regular_shape(n, dv, dc));
-    bool none = false;
-    for (int i = 0; i < count; ++i) {
-        const int32_t *c = calls + 6 * (size_t)i;
-        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
-        const BpPlan p = bp_ens_plan(n, dv, dc, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus);
-        write_plan(p, i, out, names);
-        none |= p.path == BpPath::None;
-    }
-    if (none) {
-        set_error("no ensemble soft kernel for this call (check degree > 32, or a curve beyond LDS)");
-        return LDPC_EUNSUP;
-    }
-    return LDPC_OK;
+    return write_plans(count, calls, out, names, &BpPlan::lds_slots,
+                       "no ensemble soft kernel for this call (check degree > 32, or a curve beyond LDS)",
+                       [&](int B, int iters, int algo, bool et, bool mc, bool want_post) {
+                           return bp_ens_plan(n, dv, dc, B, iters, algo, et, mc, want_post, cus);
+                       });
 }
 
 int ldpc_bp_ensemble_decode_dev(int n, int dv, int dc, const int32_t *d_check_lookup, const int32_t *d_variable_lookup,
@@ -849,16 +852,8 @@ int ldpc_bp_ensemble_decode_dev(int n, int dv, int dc, const int32_t *d_check_lo
     LDPC_TRY(ens_soft_check(n, dv, dc, algo));
     LDPC_TRY(require_device());
     if (B == 0) return LDPC_OK;
-    std::lock_guard<std::mutex> lk(g_mu);
-    Workspace &ws = workspace(stream);
-    std::lock_guard<std::mutex> wl(ws.mu);
-    const size_t sb = ens_scratch_bytes(n, dv, dc, B, max_iters, algo, early_stop != 0, false, d_post != nullptr);
-    float *scratch;
-    LDPC_ALLOCATED(get_scratch(ws, sb, scratch));
-    LDPC_HIP(launch_ens_decode(n, dv, dc, d_check_lookup, d_variable_lookup, d_llr, B, max_iters, algo, alpha,
-                               early_stop, d_post, d_hard, d_its, static_cast<hipStream_t>(stream), scratch,
-                               sb ? ws.scratch.cap : 0));
-    return LDPC_OK;
+    const SoftCall c = decode_call(B, max_iters, algo, alpha, early_stop, d_llr, d_post, d_hard, d_its);
+    return decode_entry(EnsFamily{n, dv, dc, d_check_lookup, d_variable_lookup}, c, stream);
 }
 
 int ldpc_mc_ensemble_soft_batch_dev(int n, int dv, int dc, int channel, float param, int algo, float alpha,
@@ -873,20 +868,14 @@ int ldpc_mc_ensemble_soft_batch_dev(int n, int dv, int dc, int channel, float pa
     LDPC_TRY(ens_soft_check(n, dv, dc, algo));
     LDPC_TRY(require_device());
     if (B == 0) return LDPC_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only: devices launch in parallel
-    std::lock_guard<std::mutex> wl(ws.mu);
-    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *its = ws.its.get<int32_t>(B);
-    int32_t *cut = ws.cutoff.get<int32_t>(4), *chk = nullptr, *var = nullptr;
-    const size_t sb = ens_scratch_bytes(n, dv, dc, B, max_iters, algo, early_stop != 0, true, false);
-    float *scratch;
-    LDPC_ALLOCATED(trial && its && cut && get_scratch(ws, sb, scratch));
-    // trial t: graph t (key = seed) and channel word t, as the BEC form
-    LDPC_TRY(sample_regular_locked(ws, n, dv, dc, seed, first_cw, B, chk, var, nullptr, s));
-    LDPC_HIP(launch_mc_ens(n, dv, dc, chk, var, channel, p, p2, seed, first_cw, B, max_iters, algo, alpha, early_stop,
-                           trial, its, s, scratch, sb ? ws.scratch.cap : 0));
-    LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
-    return LDPC_OK;
+    const SoftCall c = mc_call(B, max_iters, algo, alpha, early_stop, make_chan(channel, p, p2, seed), first_cw);
+    return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream,
+                    [&](Workspace &ws, const SoftCall &mc, hipStream_t s) {
+                        // trial t: graph t (key = seed) and channel word t, as the BEC form
+                        int32_t *chk = nullptr, *var = nullptr;
+                        LDPC_TRY(sample_regular_locked(ws, n, dv, dc, seed, first_cw, B, chk, var, nullptr, s));
+                        return soft_launch(ws, EnsFamily{n, dv, dc, chk, var}, mc, s);
+                    });
 }
 
 // --------------------------- ML ("optimal") erasure decoding ---------------
@@ -974,8 +963,7 @@ int ldpc_mc_ml_batch_dev(const ldpc_graph *g, int n, int dv, int dc, float eps, 
         if (ens)
             LDPC_HIP(launch_mc_bec_ensemble(n, dv, dc, chk, var, p, seed, first_cw, B, max_iters, trial, its, s));
         else
-            LDPC_HIP(launch_mc_decode(*g, LDPC_CH_BEC, p, p2, seed, first_cw, B, max_iters, 0, 1.0f, 0, trial, its,
-                                      s, nullptr, 0));
+            LDPC_HIP(launch_mc_bec(*g, p, p2, seed, first_cw, B, max_iters, trial, its, s));
         // the stop rule counts message-passing frame errors (parallel_simulator.py:226-231)
         LDPC_HIP(launch_mc_reduce(trial, its, B, max_iters, expurgation, stop_frame_errors, d_counters_mp, cut, s));
         LDPC_HIP(launch_mc_reduce_cut(du, nullptr, B, 0, -1, cut, d_counters_ml, s));

@@ -6,6 +6,8 @@
 
 #include <type_traits>
 
+#include "ldpc_internal.hpp"  // ChanArgs
+
 namespace ldpc {
 namespace {
 
@@ -112,14 +114,6 @@ __device__ __forceinline__ uint32_t pick4(uint4 r, int i) {
 __device__ __forceinline__ float u01(uint32_t x) {
     return (float)(2u * (x >> 9) + 1u) * 5.9604644775390625e-8f;
 }
-
-}  // namespace
-struct ChanArgs {  // (a member of the kernel argument structs the kernel files share: kernel_args.hpp)
-    int kind;      // LDPC_CH_*
-    float p, p2;   // see oracle_channel
-    uint32_t k0, k1;
-};
-namespace {
 
 // Channel value of variable 4g + i of a codeword from its Philox block r (all-zero codeword).
 __device__ __forceinline__ float chan_soft_word(const ChanArgs &ch, const uint4 &r, int i) {

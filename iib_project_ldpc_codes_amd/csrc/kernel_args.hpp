@@ -34,7 +34,7 @@ struct BpArgs {
     int32_t *trial;  // [B][max_iters+1]
     // generic kernel, messages in global scratch
     float *scratch;
-    size_t scratch_bytes;  // (host) bytes at scratch: the launchers refuse a layout needing more
+    size_t scratch_bytes;  // (host) bytes at scratch: the plan's, a shorter buffer has been refused
     // LDS kernel lane layout (ldpc_graph::lane_var / lane_slot)
     const int32_t *lane_var, *lane_slot;
     int lds_slots;  // generic GMEM kernel: message slots [0, lds_slots) kept in LDS
@@ -101,19 +101,27 @@ struct LayerQArgs {
     int32_t *trial;  // [B][max_iters+1]
 };
 
-inline ChanArgs make_chan(int kind, float p, float p2, uint64_t seed) {
-    ChanArgs c;
-    c.kind = kind;
-    c.p = p;
-    c.p2 = p2;
-    c.k0 = (uint32_t)seed;
-    c.k1 = (uint32_t)(seed >> 32);
-    return c;
+// The call's part of BpArgs, EnsArgs, LayerArgs or LayerQArgs (their field names agree; LayerQArgs
+// has no alpha and int8 posteriors); the family's launch fills in its graph and layout.
+template <typename Args>
+Args call_args(const SoftCall &c) {
+    Args a{};
+    a.B = c.B;
+    a.max_iters = c.max_iters;
+    if constexpr (!std::is_same<Args, LayerQArgs>::value) a.alpha = c.alpha;
+    a.llr = c.llr;
+    a.post = static_cast<decltype(a.post)>(c.post);
+    a.hard = c.hard;
+    a.its = c.its;
+    a.ch = c.ch;
+    a.first_cw = c.first_cw;
+    a.trial = c.trial;
+    return a;
 }
 
 // One entry per soft kernel family (bp_lds.hip, bp_loc_spa.hip / bp_loc_ms.hip, bp_irr.hip,
 // bp_generic.hip): launches the instantiation for (algo, early stop, Monte-Carlo) with the
-// plan's grid, LDS and scratch layout.  bp_dispatch.hip has checked the scratch buffer.
+// plan's grid, LDS and scratch layout.  The caller has checked the scratch buffer.
 hipError_t launch_lds36(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, bool et, bool mc, hipStream_t s);
 hipError_t launch_loc_spa(const BpPlan &p, const ldpc_graph &g, BpArgs a, bool et, bool mc, hipStream_t s);
 hipError_t launch_loc_ms(const BpPlan &p, const ldpc_graph &g, BpArgs a, bool et, bool mc, hipStream_t s);
@@ -123,9 +131,6 @@ hipError_t launch_generic(const BpPlan &p, const ldpc_graph &g, BpArgs a, int al
 hipError_t launch_layer(const BpPlan &p, LayerArgs a, int algo, bool et, bool mc, hipStream_t s);
 // bp_layer_q_kernel (bp_layer_q.hip), from a bp_layer_q_plan
 hipError_t launch_layer_q(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s);
-// BEC Monte-Carlo on a fixed code (bec.hip): launch_mc_decode's erasure-channel half
-hipError_t launch_mc_bec(const ldpc_graph &g, float p, float p2, uint64_t seed, uint64_t first_cw, int B,
-                         int max_iters, int32_t *trial, int32_t *trial_its, hipStream_t stream);
 // Ensemble BEC Monte-Carlo by frontier peeling (peel.hip): launch_mc_bec_ensemble's BecKernel::Peel
 // plans; trial b decodes on the (dv, dc) regular graph b of the two lists.
 hipError_t launch_mc_bec_peel(const BecPlan &plan, int n, int m, int dv, int dc, const int32_t *check_lookup,

@@ -221,14 +221,10 @@ struct BecPlan {
 // dc: the check degree of a regular graph (read under EnsMc); peel_cap > 0: a test's bound on F (peel_cap()).
 BecPlan bec_plan(int n, int m, int dc, int B, int iters, BecMode mode, int peel_cap);
 
-// Kernel launchers (bec.hip, bp_dispatch.hip, mc_kernels.hip, ml.hip).  All asynchronous on `stream`.
-// Return hipSuccess or the launch error; hipErrorInvalidValue when no kernel holds the graph.
+// Kernel launchers (bec.hip, bp_dispatch.hip, bp_ens.hip, mc_kernels.hip, ml.hip).  All asynchronous on `stream`.
+// Return hipSuccess or the launch error.
 hipError_t launch_bec_decode(const ldpc_graph &g, uint8_t *d_words, int B, int max_iters,
                              int32_t *d_errors, int32_t *d_its, hipStream_t stream);
-
-hipError_t launch_bp_decode(const ldpc_graph &g, const float *d_llr, int B, int max_iters, int algo,
-                            float alpha, int early_stop, float *d_post, uint8_t *d_hard,
-                            int32_t *d_its, hipStream_t stream, float *d_scratch, size_t scratch_bytes);
 
 // Compile-time switches read on both sides of the launch (the rest: bp_plan.cpp, the kernels' files)
 #ifndef LDPC_LDS36_PREFETCH
@@ -239,8 +235,8 @@ hipError_t launch_bp_decode(const ldpc_graph &g, const float *d_llr, int B, int 
 #endif
 
 // The launch plan of one soft-decoding call (bp_plan.cpp): which kernel runs and everything the
-// launch needs, decided in one host-only function.  The launchers, the scratch sizing and the
-// kernel-name introspection all read it; nothing else re-derives these numbers.
+// launch needs, decided in one host-only function, once per call.  The scratch request, the
+// families' launches and the kernel-name introspection all read it; nothing else re-derives these numbers.
 enum class BpPath {
     Loc, Lds36, Irr, Generic8, Generic16, Generic32, GenericG8, GenericG16, GenericG32, None,
     // bp_ens_kernel (bp_ens_plan only; listed after None so the values above stay as they were)
@@ -309,56 +305,84 @@ constexpr size_t ens_syn_bytes(size_t m) { return (2 * ((m + 31) / 32) * 4 + 15)
 // devices launch from their own host threads, and the slabs and the grid must agree per device.
 int device_cus();
 
-// Bytes of global scratch launch_bp_decode / launch_mc_decode need for this call: bp_plan's.
-// The launchers refuse (hipErrorInvalidValue) a buffer smaller than that.
-size_t bp_scratch_bytes(const ldpc_graph &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post);
+// The channel of a fused Monte-Carlo call (a member of the kernel argument structs, kernel_args.hpp)
+struct ChanArgs {
+    int kind;      // LDPC_CH_*
+    float p, p2;   // see oracle_channel
+    uint32_t k0, k1;
+};
+inline ChanArgs make_chan(int kind, float p, float p2, uint64_t seed) {
+    ChanArgs c;
+    c.kind = kind;
+    c.p = p;
+    c.p2 = p2;
+    c.k0 = (uint32_t)seed;
+    c.k1 = (uint32_t)(seed >> 32);
+    return c;
+}
+
+// One soft-decoding call, whatever the family: what the C ABI's entries (capi.cpp) fill and the
+// families below plan and launch from.  B > 0.
+struct SoftCall {
+    int B = 0, max_iters = 0, algo = 0;
+    float alpha = 1.0f;
+    bool early_stop = false;
+    bool mc = false;  // fused-channel Monte-Carlo: ch / first_cw / trial / its; otherwise llr / post / hard / its
+    const float *llr = nullptr;
+    void *post = nullptr;  // float [B][n]; int8 for the fixed-point family; nullptr: no posteriors
+    uint8_t *hard = nullptr;
+    int32_t *its = nullptr;  // [B]
+    ChanArgs ch{};
+    uint64_t first_cw = 0;
+    int32_t *trial = nullptr;  // [B][max_iters+1] per-trial curves (then launch_mc_reduce)
+};
+
+// The soft-decoding families.  Each plans a call (its bp_*_plan, host only) and launches a plan
+// it made: asynchronous on `s`, with plan.scratch bytes at `scratch` (capi.cpp's soft_launch has
+// planned once, taken them from the workspace and refused a shorter buffer).  A call without a
+// kernel: hipErrorInvalidValue from FloodFamily, hipErrorNotSupported from the others.
+struct FloodFamily {  // flooding on a fixed code (bp_dispatch.hip and the kernel files behind it)
+    const ldpc_graph &g;
+    BpPlan plan(const SoftCall &c, int cus) const {
+        return bp_plan(g, c.B, c.max_iters, c.algo, c.early_stop, c.mc, c.post != nullptr, cus);
+    }
+    hipError_t launch(const BpPlan &p, const SoftCall &c, float *scratch, hipStream_t s) const;
+};
+struct EnsFamily {  // word / trial b on graph b of the sampler's lists, int32 [B][n*dv] each, only read (bp_ens.hip)
+    int n, dv, dc;
+    const int32_t *chk, *var;
+    BpPlan plan(const SoftCall &c, int cus) const {
+        return bp_ens_plan(n, dv, dc, c.B, c.max_iters, c.algo, c.early_stop, c.mc, c.post != nullptr, cus);
+    }
+    hipError_t launch(const BpPlan &p, const SoftCall &c, float *scratch, hipStream_t s) const;
+};
+struct LayerFamily {  // layered (row-serial) schedule of graph_host.cpp's build_layer_schedule (bp_layer.hip)
+    const ldpc_graph &g;
+    BpPlan plan(const SoftCall &c, int cus) const {
+        return bp_layer_plan(g, c.B, c.max_iters, c.algo, c.early_stop, c.mc, c.post != nullptr, cus);
+    }
+    hipError_t launch(const BpPlan &p, const SoftCall &c, float *scratch, hipStream_t s) const;
+};
+struct LayerQFamily {  // fixed-point layered min-sum (bp_layer_q.hip); q validated by the caller; no scratch
+    const ldpc_graph &g;
+    const ldpc_quant &q;
+    BpPlan plan(const SoftCall &c, int cus) const {
+        return bp_layer_q_plan(g, c.B, c.max_iters, 1, c.early_stop, c.mc, c.post != nullptr, cus);
+    }
+    hipError_t launch(const BpPlan &p, const SoftCall &c, float *scratch, hipStream_t s) const;
+};
 
 hipError_t launch_channel(int channel, float p, float p2, uint64_t seed, uint64_t first_cw, int n,
                           int B, void *d_out, hipStream_t stream);
 
-// Monte-Carlo: fused channel + decode writing per-trial curves into `trial`
-// ([B][max_iters+1] int32) and its into `trial_its` ([B]); then the reducer.
-hipError_t launch_mc_decode(const ldpc_graph &g, int channel, float p, float p2, uint64_t seed,
-                            uint64_t first_cw, int B, int max_iters, int algo, float alpha,
-                            int early_stop, int32_t *trial, int32_t *trial_its, hipStream_t stream,
-                            float *d_scratch, size_t scratch_bytes);
+// Monte-Carlo: a fused channel + decode writes per-trial curves into `trial` ([B][max_iters+1]
+// int32) and its into `trial_its` ([B]); then the reducer.  launch_mc_bec (bec.hip): the erasure
+// channel on a fixed code.
+hipError_t launch_mc_bec(const ldpc_graph &g, float p, float p2, uint64_t seed, uint64_t first_cw, int B,
+                         int max_iters, int32_t *trial, int32_t *trial_its, hipStream_t stream);
 hipError_t launch_mc_reduce(const int32_t *trial, const int32_t *trial_its, int B, int max_iters,
                             int expurgation, int64_t stop_frame_errors, int64_t *d_counters,
                             int32_t *d_cutoff, hipStream_t stream);
-
-// Ensemble soft decoding (bp_ens.hip): word / trial b on graph b of (check_lookup, variable_lookup),
-// int32 [B][n*dv] each as launch_sample_regular writes them (a simple graph).  The lists are only
-// read.  Scratch: bp_ens_plan's; a shorter buffer is refused (hipErrorInvalidValue), a shape
-// without a kernel (check degree > 32) is hipErrorNotSupported.
-size_t ens_scratch_bytes(int n, int dv, int dc, int B, int iters, int algo, bool early_stop, bool mc, bool want_post);
-hipError_t launch_ens_decode(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
-                             const float *d_llr, int B, int max_iters, int algo, float alpha, int early_stop,
-                             float *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream, float *d_scratch,
-                             size_t scratch_bytes);
-hipError_t launch_mc_ens(int n, int dv, int dc, const int32_t *check_lookup, const int32_t *variable_lookup,
-                         int channel, float p, float p2, uint64_t seed, uint64_t first_cw, int B, int max_iters,
-                         int algo, float alpha, int early_stop, int32_t *trial, int32_t *trial_its,
-                         hipStream_t stream, float *d_scratch, size_t scratch_bytes);
-
-// Layered (row-serial) soft decoding on a fixed code (bp_layer.hip): the schedule of
-// graph_host.cpp's build_layer_schedule, semantics in include/ldpc_mi355x.h.  Scratch:
-// bp_layer_plan's; a shorter buffer is refused (hipErrorInvalidValue), a graph without a
-// schedule is hipErrorNotSupported.
-size_t layer_scratch_bytes(const ldpc_graph &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post);
-hipError_t launch_layer_decode(const ldpc_graph &g, const float *d_llr, int B, int max_iters, int algo, float alpha,
-                               int early_stop, float *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream,
-                               float *d_scratch, size_t scratch_bytes);
-hipError_t launch_mc_layer(const ldpc_graph &g, int channel, float p, float p2, uint64_t seed, uint64_t first_cw,
-                           int B, int max_iters, int algo, float alpha, int early_stop, int32_t *trial,
-                           int32_t *trial_its, hipStream_t stream, float *d_scratch, size_t scratch_bytes);
-
-// Fixed-point layered min-sum (bp_layer_q.hip), semantics in include/ldpc_mi355x.h; q validated by
-// the caller.  No scratch.  hipErrorNotSupported: no schedule, or the block does not fit LDS.
-hipError_t launch_layer_q_decode(const ldpc_graph &g, const float *d_llr, int B, int max_iters, const ldpc_quant &q,
-                                 int early_stop, int8_t *d_post, uint8_t *d_hard, int32_t *d_its, hipStream_t stream);
-hipError_t launch_mc_layer_q(const ldpc_graph &g, int channel, float p, float p2, uint64_t seed, uint64_t first_cw,
-                             int B, int max_iters, const ldpc_quant &q, int early_stop, int32_t *trial,
-                             int32_t *trial_its, hipStream_t stream);
 
 // Buckets (= threads per workgroup) of the parallel graph sampler for n*dv
 // sockets; the permutation is in LDS (u16) when n*dv < 65536.  Must match

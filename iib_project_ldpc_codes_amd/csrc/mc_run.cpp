@@ -344,7 +344,9 @@ struct SeqBackend {
     }
 };
 
-int check_common(int channel, int max_iters, int batch, const int *devices, int ndev, int64_t *counters) {
+// What ldpc_mc_run and ldpc_mc_run_csr share: the checks, then the run's decoding settings (the graph source is theirs)
+int run_common(Run &r, int channel, float param, int algo, float alpha, int early_stop, uint64_t seed, int max_iters,
+               int expurgation, int batch, const int *devices, int ndev, int64_t *counters) {
     LDPC_REQUIRE(counters && devices && ndev > 0 && max_iters >= 0 && batch > 0,
                  "ldpc_mc_run: need counters, devices[ndev > 0], max_iters >= 0, batch > 0");
     LDPC_REQUIRE(channel == LDPC_CH_BEC || channel == LDPC_CH_BSC || channel == LDPC_CH_AWGN,
@@ -360,6 +362,8 @@ int check_common(int channel, int max_iters, int batch, const int *devices, int 
             LDPC_REQUIRE(devices[j] != devices[i],
                          "ldpc_mc_run: a device is listed twice (RCCL needs one rank per device)");
     }
+    r.channel = channel; r.param = param; r.algo = algo; r.alpha = alpha; r.early_stop = early_stop;
+    r.seed = seed; r.max_iters = max_iters; r.expurgation = expurgation; r.batch = batch;
     return LDPC_OK;
 }
 
@@ -371,16 +375,15 @@ int ldpc_mc_run(const int32_t *variable_to_check_list, const int32_t *check_to_v
                 int dc, int channel, float param, int algo, float alpha, int early_stop, uint64_t seed,
                 int max_iters, int expurgation, int64_t num_tests, int64_t stop_frame_errors, int batch,
                 double time_limit_s, const int *devices, int ndev, int64_t *counters, int64_t *rounds) {
-    LDPC_TRY(check_common(channel, max_iters, batch, devices, ndev, counters));
     Run r;
+    LDPC_TRY(run_common(r, channel, param, algo, alpha, early_stop, seed, max_iters, expurgation, batch, devices, ndev,
+                        counters));
     r.ensemble = (variable_to_check_list == nullptr && check_to_variable_list == nullptr);
     LDPC_REQUIRE(r.ensemble || (variable_to_check_list && check_to_variable_list),
                  "ldpc_mc_run: give both edge lists (fixed code) or neither (ensemble)");
     r.v2c = variable_to_check_list;
     r.c2v = check_to_variable_list;
     r.n = n; r.k = k; r.dv = dv; r.dc = dc;
-    r.channel = channel; r.param = param; r.algo = algo; r.alpha = alpha; r.early_stop = early_stop;
-    r.seed = seed; r.max_iters = max_iters; r.expurgation = expurgation; r.batch = batch;
     std::lock_guard<std::mutex> lk(g_run_mu);
     return run_impl(r, num_tests, stop_frame_errors, time_limit_s, devices, ndev, counters, rounds);
 }
@@ -390,13 +393,12 @@ int ldpc_mc_run_csr(const int32_t *check_ptr, const int32_t *check_var, const in
                     int early_stop, uint64_t seed, int max_iters, int expurgation, int64_t num_tests,
                     int64_t stop_frame_errors, int batch, double time_limit_s, const int *devices, int ndev,
                     int64_t *counters, int64_t *rounds) {
-    LDPC_TRY(check_common(channel, max_iters, batch, devices, ndev, counters));
-    LDPC_REQUIRE(check_ptr && check_var && var_ptr && var_slot, "ldpc_mc_run_csr: null CSR array");
     Run r;
+    LDPC_TRY(run_common(r, channel, param, algo, alpha, early_stop, seed, max_iters, expurgation, batch, devices, ndev,
+                        counters));
+    LDPC_REQUIRE(check_ptr && check_var && var_ptr && var_slot, "ldpc_mc_run_csr: null CSR array");
     r.cptr = check_ptr; r.cvar = check_var; r.vptr = var_ptr; r.vslot = var_slot;
     r.n = n; r.m = m;
-    r.channel = channel; r.param = param; r.algo = algo; r.alpha = alpha; r.early_stop = early_stop;
-    r.seed = seed; r.max_iters = max_iters; r.expurgation = expurgation; r.batch = batch;
     std::lock_guard<std::mutex> lk(g_run_mu);
     return run_impl(r, num_tests, stop_frame_errors, time_limit_s, devices, ndev, counters, rounds);
 }
