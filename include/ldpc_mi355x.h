@@ -17,6 +17,30 @@
  * shape checks); the per-codeword buffers may then be NULL (an empty device
  * tensor's data pointer).  max_iters = 0: BEC words are left as they are with
  * its = 0; soft decoders return the channel LLRs as posteriors.
+ *
+ * Streams: every `_dev` entry is asynchronous on `stream`.  All its device work --
+ * kernels, the memsets that reset the persistent grid's codeword counter and the
+ * sampler's search control, the Monte-Carlo cutoff and reduction -- is issued on
+ * `stream` and nowhere else, so it is ordered after what the caller queued there
+ * before the call (inputs may still be in flight) and before what is queued
+ * afterwards; nothing is read or reset when the call is enqueued.  Calls may be
+ * queued on one stream without a host synchronisation in between.  Monte-Carlo
+ * batches queued into one counters tensor stop exactly: each batch reads
+ * counters[1] on the device when it runs, counts the trials up to the one that
+ * reaches stop_frame_errors, and later batches add nothing.
+ * Scratch (trial rows, message slabs, sampler control, the host forms' staging)
+ * lives in grow-only workspaces, one per (device, stream): calls on different
+ * streams or devices never share it, and may be issued from different host threads
+ * (ldpc_last_error() is per thread).  A workspace grows by freeing and
+ * reallocating, which synchronises the whole device: the first call of a larger
+ * shape on a (device, stream) blocks the host until the device is idle; calls of
+ * shapes already seen there do not block.  ldpc_sample_csr_dev always blocks: it
+ * synchronises `stream` before it rewrites the degree structure an earlier launch
+ * may still read, and uploads it with a synchronous copy.  The host-pointer forms
+ * block until their result is on the host; they stage through the workspace of the
+ * NULL stream (message_passing: through its own cached buffers and stream).
+ * Because workspaces allocate, the entries cannot be captured into a HIP graph.
+ * (tests/test_gpu_streams.py)
  */
 #ifndef LDPC_MI355X_H
 #define LDPC_MI355X_H
