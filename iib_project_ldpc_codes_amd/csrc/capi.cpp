@@ -349,6 +349,22 @@ int ldpc_debug_bec_plan(int n, int m, int dc, int count, const int32_t *calls, i
     return LDPC_OK;
 }
 
+// The launch plan (sample_plan) of one sampler call, from the shape alone; out / names: the header's.
+int ldpc_debug_sample_plan(int n, int m, int E, int max_cdeg, int max_vdeg, int regular, int dv, int G, int cus,
+                           int64_t *out, char *names) {
+    LDPC_REQUIRE(n > 0 && m > 0 && E > 0 && max_cdeg > 0 && max_vdeg > 0 && G >= 0 && cus >= 0 && out && names &&
+                     (!regular || dv > 0),
+                 "bad plan arguments");
+    const SamplePlan p = sample_plan(n, m, E, max_cdeg, max_vdeg, regular != 0, dv, G, cus);
+    const int64_t row[16] = {p.seq, p.threads, p.K, (int64_t)p.lds, p.bw, p.ring, p.fb, p.fbu,
+                             p.emit_fb, (int64_t)p.mdv, p.V, p.nch, p.row, (int64_t)p.vs_lds, p.per_cu, p.W};
+    std::copy(row, row + 16, out);
+    snprintf(names, 64, "%s", p.draw);
+    snprintf(names + 64, 64, "%s", p.var_side);
+    snprintf(names + 128, 64, "%s", p.search);
+    return LDPC_OK;
+}
+
 const char *ldpc_bp_kernel_name(const ldpc_graph *g, int early_stop) {
     return g ? bp_kernel_name(*g, early_stop) : "none";
 }

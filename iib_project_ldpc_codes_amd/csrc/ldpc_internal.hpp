@@ -1,4 +1,4 @@
-// Internal declarations shared by the host files (capi.cpp, graph_host.cpp, graph_device.cpp, bp_plan.cpp, bec_plan.cpp) and the kernels
+// Internal declarations shared by the host files (capi.cpp, graph_host.cpp, graph_device.cpp, bp_plan.cpp, bec_plan.cpp, sample_plan.cpp) and the kernels
 // (bec.hip, bp_*.hip, mc_kernels.hip, ml.hip, sampler.hip, peel.hip).  Not part of the public ABI (see include/ldpc_mi355x.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -392,6 +392,42 @@ inline int sample_buckets(int E) { return E <= 16384 ? 256 : (E < 65536 ? 512 : 
 // kSeqMinE <= n*dv <= kSeqMaxE with check degrees <= kSeqMaxCdeg; the oracle's
 // SEQ_* constants must equal these.  Larger graphs: one level, K = 1024.
 constexpr int kSeqMinE = 8192, kSeqMaxE = 393216, kSeqMaxCdeg = 192;
+// LDS of one sequential-draw attempt (sampler.hip asserts its carve against this): 344 words of
+// sync words, retry lists and last pool entries, a ring of 512 entries of ring_bytes each (2: u16
+// variable ids, 4: int), then the pool bitmap of bw words.
+constexpr int kSeqThreads = 128, kSeqRingSlots = 512, kSeqFixedWords = 344;
+constexpr size_t seq_plan_lds(int bw, int ring_bytes) {
+    return (size_t)4 * ((size_t)bw + kSeqFixedWords) + (size_t)ring_bytes * kSeqRingSlots;
+}
+
+// The launch plan of one sampler call (sample_plan.cpp): which kernels run and everything their
+// launches need, decided in one host-only function; sampler.hip launches what it says.
+struct SamplePlan {
+    bool seq = false;           // the sequential-draw sampler (else one Rao-Sandelius level)
+    bool csr = false;           // irregular degree structure
+    const char *draw = "none";  // sample_seq_kernel<regular|csr,u16|int> or sample_regular_kernel<K,u16|int32,lds|gmem>
+    int threads = 0;            // of the draw kernel
+    int K = 0;                  // one level: buckets (= threads); 0 for the sequential sampler
+    size_t lds = 0;             // dynamic LDS bytes of the draw kernel (and of the search pass)
+    int bw = 0;                 // sequential: bitmap words (a multiple of 4, 32 bw >= E)
+    int ring = 0;               // sequential: bytes of a ring entry (2: u16 when n <= 65,536, else 4)
+    int fb = 0;                 // sequential: bits of a variable's occurrence counter (0: max degree >= 256)
+    int fbu = 0;                // fb when n counters fit the bitmap's LDS, else 0 (global CAS)
+    int emit_fb = 0;            // what the emit pass is told: -1 (the variable-side kernel follows) or fbu
+    uint32_t mdv = 0;           // regular: ceil(2^32 / dv) for socket / dv by multiply-high, 0: true divide
+    const char *var_side = "none";  // sample_var_side_kernel<1024,u16|int32> when V > 0
+    int V = 0;                  // variables per variable-side workgroup (a multiple of 64; 0: no such kernel)
+    int nch = 0;                // chunks of V variables per graph
+    int row = 0;                // bytes of a staged row entry (2: every check / slot id below 65,536, else 4)
+    size_t vs_lds = 0;          // dynamic LDS bytes of the variable-side kernel
+    const char *search = "none";    // sample_search_kernel<regular|csr,u16|int> when W > 0
+    int per_cu = 0;             // search workgroups one CU holds (LDS bound)
+    int W = 0;                  // persistent workgroups of the search pass (0: no search pass)
+};
+// (n, m, E): variables, checks, sockets; max_cdeg / max_vdeg: the largest degrees; regular: the
+// (dv, dc) structure (dv is read only then); G graphs; cus: compute units of the device, 0 for
+// the single-pass form without a search pass.
+SamplePlan sample_plan(int n, int m, int E, int max_cdeg, int max_vdeg, bool regular, int dv, int G, int cus);
 
 // Random regular graphs on the device (law of random_code_generator.c), one
 // workgroup per graph; attempts[g] = number of permutations drawn (negative if

@@ -152,6 +152,7 @@ constexpr int kSeqSlots = 2 * kSeqT;           // slots per round: two per lane
 constexpr int kSeqRing = 512;                  // ring: a round + the longest check it completes
 static_assert(kSeqSlots + kSeqMaxCdeg <= kSeqRing, "the ring must hold a round and the check it completes");
 static_assert(kSeqNW == 2, "the cut words hold two waves");
+static_assert(kSeqT == kSeqThreads && kSeqRing == kSeqRingSlots, "sample_plan's workgroup and ring");
 static_assert(kSeqMaxE <= (1 << 19), "first-pass keys: an entry in 19 bits, the word index above bit 20");
 // LDS sync words of an attempt: reject flags by round parity [0, 2), per parity and wave the two lowest
 // colliding slots and the lowest one's pick [2, 14), the pick's owner per wave [14, 16), the
@@ -688,6 +689,9 @@ __host__ __device__ constexpr size_t seq_lds_bytes(int bw) {
     return (size_t)4 * (bw + kSeqFinal + 2 * kSeqT + kSeqSync) + sizeof(RT) * kSeqRing;
 }
 
+static_assert(seq_lds_bytes<uint16_t>(0) == seq_plan_lds(0, 2) && seq_lds_bytes<int>(4) == seq_plan_lds(4, 4),
+              "sample_plan sizes the LDS of this carve");
+
 template <typename RT>
 __device__ __forceinline__ SeqCtx seq_ctx(const SampleShape &sh, uint32_t k0, uint32_t k1, uint64_t gid, uint32_t mdv,
                                          unsigned char *smem, int bw) {
@@ -1071,91 +1075,70 @@ __global__ __launch_bounds__(T) void sample_regular_kernel(SampleShape sh, uint3
 
 }  // namespace
 
+// Launches what sample_plan (sample_plan.cpp) says: the draw kernel (after the search pass when
+// `ctl` is given), then the variable-side kernel where the plan has one.
 static hipError_t launch_sample(const SampleShape &sh, int max_cdeg, int max_vdeg, uint64_t seed,
                                 uint64_t first_graph, int G, int32_t *check_lookup, int32_t *variable_lookup,
                                 int32_t *attempts, int max_attempts, uint32_t *ctl, hipStream_t stream) {
     if (G <= 0) return hipSuccess;
-    const int E = sh.E;
-    const int K = sample_buckets(E);
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const size_t ctl_lds = (size_t)4 * (K * (K / kWave) + 16);
-    const bool u16 = sh.n <= 65536;
+    const bool csr = sh.vsock != nullptr;
+    // the plan without a device first; the device is asked for its CUs only where a search pass
+    // can run (a sequential plan and `ctl` given), and the plan made again with them
+    SamplePlan p = sample_plan(sh.n, sh.m, sh.E, max_cdeg, max_vdeg, !csr, sh.dv, G, 0);
+    hipError_t e = hipSuccess;
+    if (p.seq && ctl) {
+        int dev = 0, cus = 0;
+        e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) return e;
+        p = sample_plan(sh.n, sh.m, sh.E, max_cdeg, max_vdeg, !csr, sh.dv, G, cus);
+    }
 #define LDPC_SAMPLE(TT, IDX, LDSB)                                                                             \
     do {                                                                                                       \
         auto k = sample_regular_kernel<TT, IDX, LDSB>;                                                         \
-        const size_t lds = ctl_lds + (LDSB ? (size_t)2 * E : 0);                                                   \
-        hipError_t e = allow_lds(k, lds);                                                                      \
-        if (e != hipSuccess) return e;                                                                         \
-        hipLaunchKernelGGL(k, dim3(G), dim3(TT), lds, stream, sh, k0, k1, first_graph, check_lookup,           \
+        if ((e = allow_lds(k, p.lds)) != hipSuccess) return e;                                                 \
+        hipLaunchKernelGGL(k, dim3(G), dim3(TT), p.lds, stream, sh, k0, k1, first_graph, check_lookup,         \
                            variable_lookup, attempts, max_attempts);                                           \
         return hipGetLastError();                                                                              \
     } while (0)
-    const bool seq = E >= kSeqMinE && E <= kSeqMaxE && max_cdeg <= kSeqMaxCdeg;
-    if (K == 256 && u16 && !seq) LDPC_SAMPLE(256, uint16_t, true);
-    if (K == 512 && u16 && !seq) LDPC_SAMPLE(512, uint16_t, true);
-    if (seq) {
-        // bitmap words (a multiple of 4: cleared with 16-byte stores); rank counters of
-        // fb bits per variable share them when they fit
-        int bw = ((E + 31) / 32 + 3) & ~3;
-        const int fb = max_vdeg <= 3 ? 2 : (max_vdeg <= 15 ? 4 : (max_vdeg <= 255 ? 8 : 0));
-        const int fbu = fb && (long)sh.n * fb <= (long)bw * 32 ? fb : 0;
-        const bool r16 = sh.n <= 65536;  // variable ids fit the u16 ring
-        const size_t lds = r16 ? seq_lds_bytes<uint16_t>(bw) : seq_lds_bytes<int>(bw);
-        auto kern = sh.vsock ? (r16 ? sample_seq_kernel<true, uint16_t> : sample_seq_kernel<true, int>)
-                             : (r16 ? sample_seq_kernel<false, uint16_t> : sample_seq_kernel<false, int>);
-        hipError_t e = allow_lds(kern, lds);
-        if (e != hipSuccess) return e;
-        const uint32_t mdv =
-            sh.vsock == nullptr && sh.dv > 1 && sh.dv < 256 ? (uint32_t)((0x100000000ull + sh.dv - 1) / sh.dv) : 0u;
-        const uint32_t *start = nullptr, *homewin = nullptr;
-        if (ctl) {
-            // search pass: persistent workgroups of kSeqNW waves, as many as fit the device (LDS
-            // bound), at most one pool row each in the 2G rows of the two outputs
-            int dev = 0, cus = 0;
-            e = hipGetDevice(&dev);
-            if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            if (e != hipSuccess) return e;
-            const long per_cu = std::max<long>(1, std::min<long>(32, (long)(160 * 1024) / (long)lds));
-            const int W = (int)std::min<long>((long)G, (long)cus * per_cu);
-            auto sk = sh.vsock ? (r16 ? sample_search_kernel<true, uint16_t> : sample_search_kernel<true, int>)
-                               : (r16 ? sample_search_kernel<false, uint16_t> : sample_search_kernel<false, int>);
-            if ((e = allow_lds(sk, lds)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(ctl, 0, 8, stream)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(ctl + 2, 0xFF, (size_t)4 * G, stream)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(ctl + 2 + G, 0, (size_t)4 * G, stream)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(ctl + 2 + 2 * G, 0xFF, (size_t)4 * G, stream)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(ctl + 2 + 3 * G, 0, (size_t)4 * G, stream)) != hipSuccess) return e;
-            // graphs' home waves draw into check_lookup; pool rows: wave w uses variable_lookup row w
-            hipLaunchKernelGGL(sk, dim3(W), dim3(kSeqT), lds, stream, sh, k0, k1, first_graph, G, check_lookup,
-                               variable_lookup, ctl, max_attempts, bw, mdv);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            start = ctl + 2;
-            homewin = ctl + 2 + 2 * G;
-        }
-        // variable side: chunks of V variables per workgroup after the emit pass, rows of at most
-        // max_vdeg entries staged in LDS (u16 entries when they fit) within ~150 KB
-        const bool u16rows = sh.vsock ? sh.E <= 65536 : sh.m <= 65536;
-        const size_t rb = u16rows ? 2 : 4;
-        int V = 0;
-        if (fb) {
-            const size_t bits = 8 * rb * (size_t)max_vdeg + (size_t)fb;  // LDS bits per variable
-            V = (int)std::min<size_t>((size_t)sh.n, (size_t)150 * 1024 * 8 / bits) & ~63;
-            if (V < 64) V = 0;
-        }
-        hipLaunchKernelGGL(kern, dim3(G), dim3(kSeqT), lds, stream, sh, k0, k1, first_graph,
-                           check_lookup, variable_lookup, attempts, max_attempts, bw, V ? -1 : fbu, mdv, start,
-                           homewin);
-        if ((e = hipGetLastError()) != hipSuccess || !V) return e;
-        const int nch = (sh.n + V - 1) / V;
-        const size_t vs_lds = (size_t)4 * (((long)V * fb + 31) / 32 + 3) / 4 * 4 + rb * (size_t)V * max_vdeg;
-        auto vk = u16rows ? sample_var_side_kernel<1024, uint16_t> : sample_var_side_kernel<1024, int32_t>;
-        if ((e = allow_lds(vk, vs_lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(vk, dim3((unsigned)G * nch), dim3(1024), vs_lds, stream, sh, check_lookup, variable_lookup,
-                           G, V, fb, max_vdeg);
-        return hipGetLastError();
+    if (!p.seq) {
+        if (p.K == 256) LDPC_SAMPLE(256, uint16_t, true);
+        if (p.K == 512) LDPC_SAMPLE(512, uint16_t, true);
+        LDPC_SAMPLE(1024, int32_t, false);
     }
-    LDPC_SAMPLE(1024, int32_t, false);
 #undef LDPC_SAMPLE
+    const bool r16 = p.ring == 2;
+    auto kern = csr ? (r16 ? sample_seq_kernel<true, uint16_t> : sample_seq_kernel<true, int>)
+                    : (r16 ? sample_seq_kernel<false, uint16_t> : sample_seq_kernel<false, int>);
+    if ((e = allow_lds(kern, p.lds)) != hipSuccess) return e;
+    const uint32_t *start = nullptr, *homewin = nullptr;
+    if (p.W) {
+        // search pass: p.W persistent workgroups, at most one pool row each in the 2G rows of the
+        // two outputs
+        auto sk = csr ? (r16 ? sample_search_kernel<true, uint16_t> : sample_search_kernel<true, int>)
+                      : (r16 ? sample_search_kernel<false, uint16_t> : sample_search_kernel<false, int>);
+        if ((e = allow_lds(sk, p.lds)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(ctl, 0, 8, stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(ctl + 2, 0xFF, (size_t)4 * G, stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(ctl + 2 + G, 0, (size_t)4 * G, stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(ctl + 2 + 2 * G, 0xFF, (size_t)4 * G, stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(ctl + 2 + 3 * G, 0, (size_t)4 * G, stream)) != hipSuccess) return e;
+        // graphs' home waves draw into check_lookup; pool rows: wave w uses variable_lookup row w
+        hipLaunchKernelGGL(sk, dim3(p.W), dim3(kSeqT), p.lds, stream, sh, k0, k1, first_graph, G, check_lookup,
+                           variable_lookup, ctl, max_attempts, p.bw, p.mdv);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        start = ctl + 2;
+        homewin = ctl + 2 + 2 * G;
+    }
+    hipLaunchKernelGGL(kern, dim3(G), dim3(kSeqT), p.lds, stream, sh, k0, k1, first_graph, check_lookup,
+                       variable_lookup, attempts, max_attempts, p.bw, p.emit_fb, p.mdv, start, homewin);
+    if ((e = hipGetLastError()) != hipSuccess || !p.V) return e;
+    auto vk = p.row == 2 ? sample_var_side_kernel<1024, uint16_t> : sample_var_side_kernel<1024, int32_t>;
+    if ((e = allow_lds(vk, p.vs_lds)) != hipSuccess) return e;
+    hipLaunchKernelGGL(vk, dim3((unsigned)G * p.nch), dim3(1024), p.vs_lds, stream, sh, check_lookup, variable_lookup,
+                       G, p.V, p.fb, max_vdeg);
+    return hipGetLastError();
 }
 
 hipError_t seq_stats(uint64_t *out, int reset) {

@@ -557,6 +557,27 @@ int ldpc_quant_check(const ldpc_quant *q);
 int ldpc_debug_bec_plan(int n, int m, int dc, int count, const int32_t *calls, int64_t *out, char *names);
 
 /*
+ * Host-only: the launch plan of one graph-sampler call (csrc/sample_plan.cpp sample_plan), from
+ * the shape alone: n variables, m checks, E sockets, the largest check and variable degree,
+ * regular != 0 for the (dv, dc) structure of ldpc_sample_regular (dv is read only then; pass
+ * max_cdeg = dc, max_vdeg = dv), G graphs, and cus compute units (0: the single-pass form, no
+ * search pass).  out int64[16] = {sequential (1) or one-level (0) sampler, threads of the draw
+ * kernel, K buckets (0 for the sequential sampler), its dynamic LDS bytes, bw bitmap words,
+ * bytes of a ring entry (2 | 4), fb counter bits (2 | 4 | 8, 0 from degree 256), fbu (fb when
+ * the counters fit the bitmap's LDS), the emit pass's fb argument (-1: the variable-side kernel
+ * follows), mdv = ceil(2^32 / dv) or 0 for the true divide (dv = 1, dv >= 256, irregular), V
+ * variables per variable-side workgroup (0: no such kernel), nch chunks per graph, bytes of a
+ * staged row entry (2 | 4), the variable-side kernel's dynamic LDS bytes, search workgroups
+ * per CU, W persistent workgroups of the search pass (0: none)}; columns 4.. are 0 for the
+ * one-level sampler.  names char[3][64]: the draw kernel (sample_seq_kernel<regular|csr,
+ * u16|int>, sample_regular_kernel<256,u16,lds>, <512,u16,lds> or <1024,int32,gmem>), the
+ * variable-side kernel (sample_var_side_kernel<1024,u16|int32> or none) and the search
+ * kernel (sample_search_kernel<regular|csr,u16|int> or none).
+ */
+int ldpc_debug_sample_plan(int n, int m, int E, int max_cdeg, int max_vdeg, int regular, int dv, int G, int cus,
+                           int64_t *out, char *names);
+
+/*
  * Host-only: ldpc_mc_run's round accounting (csrc/mc_plan.hpp: per-slot batch clamp to
  * num_tests, the crossing slot's cut at its share of the remaining frame errors, later slots
  * dropped) driven by the same loop as the device run, on a synthetic trial sequence:

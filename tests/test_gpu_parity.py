@@ -658,8 +658,13 @@ def test_device_sampler_matches_oracle(torch, n, dv, dc):
 
 @pytest.mark.parametrize("n", [2000, 20000, 30000])
 def test_device_irregular_sampler_matches_oracle(torch, n):
-    """ldpc_sample_csr (RSU rate-1/2 degree structure) == oracle_sample_csr, bit for bit;
-    n = 2000 / 20000 use the LDS permutation (256 / 512 buckets), 30000 the global one."""
+    """ldpc_sample_csr (RSU rate-1/2 degree structure) == oracle_sample_csr, bit for bit.  By
+    the launch plan (ldpc_debug_sample_plan): n = 2000 (E = 5,723) runs the one-level sampler with
+    the permutation in LDS, sample_regular_kernel<256,u16,lds>; n = 20000 (E = 57,238) and 30000
+    (E = 85,857) run the sequential sampler, sample_seq_kernel<csr,u16> behind its search pass,
+    with 4-bit occurrence counters and sample_var_side_kernel<1024,u16> (slot ids below 65,536)
+    or <1024,int32>.  The one-level kernels on 512 and 1024 buckets are held by
+    tests/test_gpu_sampler_shapes.py."""
     from iib_project_ldpc_codes_amd import _native, ensembles
     vptr, cptr = ensembles.degree_ptrs(ensembles.RSU_DL4, n)
     E, m, G = int(vptr[-1]), len(cptr) - 1, 4
