@@ -92,6 +92,9 @@ SIGNATURES = {
     "ldpc_mc_ensemble_soft_batch_dev": ([i, i, i, i, f, i, f, i, u64, u64, i, i, i, i64, P, P], i),
     "ldpc_debug_ens_plan": ([i, i, i, i, P, i, P, P], i),
     "ldpc_debug_bec_plan": ([i, i, i, i, P, P, P], i),
+    "ldpc_gb_decode_batch_dev": ([P, P, i, i, i, i, P, P, P], i),
+    "ldpc_mc_gb_batch_dev": ([P, f, u64, u64, i, i, i, i, i, i64, P, P], i),
+    "ldpc_debug_gb_plan": ([i, i, i, P, P, P], i),
     "ldpc_debug_sample_plan": ([i, i, i, i, i, i, i, i, i, P, P], i),
     "ldpc_sample_csr_dev": ([i, i, P, P, u64, u64, i, P, P, P, P], i),
     "ldpc_sample_csr": ([i, i, P, P, u64, u64, i, P, P, P], i),

@@ -538,6 +538,73 @@ int ldpc_mc_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t se
                     });
 }
 
+// --------------------------- Gallager A/B (gb.hip) -------------------------
+// The checks the two Gallager entries share: LDPC_EINVAL for bad arguments, LDPC_EUNSUP for a
+// variable degree beyond the four count planes or planes that fit LDS at no plane word
+static int gb_check(const ldpc_graph *g, int B, int max_iters, int b, bool es, bool mc, GbPlan &plan) {
+    LDPC_REQUIRE(g && B >= 0 && max_iters >= 0, "bad Gallager A/B arguments");
+    LDPC_REQUIRE(b >= 0 && b <= kGbMaxB, "flip threshold b must be 0 (Gallager A) .. 14");
+    LDPC_REQUIRE(g->consistent,
+                 "Gallager decoding needs consistent edge lists (each (v,c) pair listed equally often on both sides)");
+    if (g->max_vdeg > kGbMaxVdeg) {
+        set_error("Gallager A/B counts disagreements in four planes: variable degrees up to 15");
+        return LDPC_EUNSUP;
+    }
+    plan = gb_plan(g->n, g->E, B, max_iters, es, mc);
+    if (!plan.threads) {
+        set_error("the Gallager A/B planes (one word per slot and variable) fit LDS at no plane word");
+        return LDPC_EUNSUP;
+    }
+    return LDPC_OK;
+}
+
+int ldpc_gb_decode_batch_dev(const ldpc_graph *g, const uint8_t *d_bits, int B, int max_iters, int b, int early_stop,
+                             uint8_t *d_hard, int32_t *d_its, void *stream) {
+    GbPlan plan;
+    LDPC_TRY(gb_check(g, B, max_iters, b, early_stop != 0, false, plan));
+    LDPC_REQUIRE(B == 0 || d_bits, "null received bits");
+    if (B == 0) return LDPC_OK;
+    LDPC_HIP(launch_gb_decode(plan, *g, d_bits, B, max_iters, b, early_stop != 0, d_hard, d_its,
+                              static_cast<hipStream_t>(stream)));
+    return LDPC_OK;
+}
+
+int ldpc_mc_gb_batch_dev(const ldpc_graph *g, float p, uint64_t seed, uint64_t first_cw, int B, int max_iters, int b,
+                         int early_stop, int expurgation, int64_t stop_frame_errors, int64_t *d_counters,
+                         void *stream) {
+    GbPlan plan;
+    LDPC_TRY(gb_check(g, B, max_iters, b, early_stop != 0, true, plan));
+    LDPC_REQUIRE(d_counters, "null counters");
+    float cp, cp2;
+    LDPC_TRY(channel_params(LDPC_CH_BSC, p, &cp, &cp2));
+    if (B == 0) return LDPC_OK;
+    const SoftCall c = mc_call(B, max_iters, 0, 1.0f, early_stop, make_chan(LDPC_CH_BSC, cp, cp2, seed), first_cw);
+    return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream,
+                    [&](Workspace &, const SoftCall &mc, hipStream_t s) {
+                        LDPC_HIP(launch_mc_gb(plan, *g, mc.ch, mc.first_cw, B, max_iters, b, mc.early_stop, mc.trial,
+                                              mc.its, s));
+                        return (int)LDPC_OK;
+                    });
+}
+
+// The launch plans (gb_plan) of `count` Gallager A/B calls on a graph of n variables and E slots,
+// from the shape alone.  calls[i] = {B, iters, early_stop, mc}; out + 8 i = {threads, W, plane
+// bytes, codewords per workgroup, grid, LDS bytes, LDS cap, scratch bytes}; names + 64 i: the
+// kernel's display name.  A call whose planes fit at no plane word is a row of zeros named "none".
+int ldpc_debug_gb_plan(int n, int E, int count, const int32_t *calls, int64_t *out, char *names) {
+    LDPC_REQUIRE(n > 0 && E > 0 && count >= 0 && (count == 0 || (calls && out && names)), "bad plan arguments");
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 4 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        const GbPlan p = gb_plan(n, E, c[0], c[1], c[2] != 0, c[3] != 0);
+        int64_t *o = out + 8 * (size_t)i;
+        o[0] = p.threads; o[1] = p.W; o[2] = p.plane; o[3] = p.cw_per_wg; o[4] = p.grid; o[5] = (int64_t)p.lds;
+        o[6] = (int64_t)p.cap; o[7] = (int64_t)p.scratch;
+        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+    }
+    return LDPC_OK;
+}
+
 // --------------------------- layered schedule ------------------------------
 // The argument checks the two layered entries share; LDPC_EUNSUP for a graph without a schedule
 static int layered_check(const ldpc_graph *g, int algo) {

@@ -101,6 +101,20 @@ struct LayerQArgs {
     int32_t *trial;  // [B][max_iters+1]
 };
 
+// gb_kernel (gb.hip): Gallager A/B on bit planes
+struct GbArgs {
+    const int32_t *cptr, *cvar, *vptr, *vslot;
+    int n, m, E, dv, dc;  // dv, dc > 0: regular (pointers implicit)
+    int B, max_iters, b;  // b: the flip threshold, 0 = Gallager A
+    const uint8_t *bits;  // [B][n], bit 0 of each byte
+    uint8_t *hard;        // [B][n] or nullptr
+    int32_t *its;         // [B] or nullptr (Monte-Carlo: the trial iteration counts)
+    // Monte-Carlo mode
+    ChanArgs ch;
+    uint64_t first_cw;
+    int32_t *trial;  // [B][max_iters+1]
+};
+
 // The call's part of BpArgs, EnsArgs, LayerArgs or LayerQArgs (their field names agree; LayerQArgs
 // has no alpha and int8 posteriors); the family's launch fills in its graph and layout.
 template <typename Args>

@@ -221,6 +221,23 @@ struct BecPlan {
 // dc: the check degree of a regular graph (read under EnsMc); peel_cap > 0: a test's bound on F (peel_cap()).
 BecPlan bec_plan(int n, int m, int dc, int B, int iters, BecMode mode, int peel_cap);
 
+// The launch plan of one Gallager A/B call (gb_plan.cpp): gb_kernel's instantiation, grid and LDS,
+// decided in one host-only function; gb.hip launches what it says.  One workgroup decodes one plane
+// word of codewords (8 * plane of them); threads == 0: the planes fit LDS at no plane word.
+constexpr size_t kGbLdsCap = kLdsMax - 4096;
+constexpr int kGbMaxVdeg = 15, kGbMaxB = 14;  // four count planes
+struct GbPlan {
+    const char *name = "none";  // display name, e.g. gb_kernel<1024,u16,es,mc>
+    int threads = 0;
+    int W = 0, plane = 0;    // plane words per slot (1) and bytes of one (4: u32, 2: u16, 1: u8)
+    int cw_per_wg = 0;
+    int64_t grid = 0;
+    size_t lds = 0;          // dynamic LDS bytes
+    size_t cap = 0;          // the cap `lds` was admitted under (kGbLdsCap)
+    size_t scratch = 0;      // Monte-Carlo: bytes of the trial rows and iteration counts; else 0
+};
+GbPlan gb_plan(int n, int E, int B, int iters, bool early_stop, bool mc);
+
 // Kernel launchers (bec.hip, bp_dispatch.hip, bp_ens.hip, mc_kernels.hip, ml.hip).  All asynchronous on `stream`.
 // Return hipSuccess or the launch error.
 hipError_t launch_bec_decode(const ldpc_graph &g, uint8_t *d_words, int B, int max_iters,
@@ -383,6 +400,12 @@ hipError_t launch_mc_bec(const ldpc_graph &g, float p, float p2, uint64_t seed, 
 hipError_t launch_mc_reduce(const int32_t *trial, const int32_t *trial_its, int B, int max_iters,
                             int expurgation, int64_t stop_frame_errors, int64_t *d_counters,
                             int32_t *d_cutoff, hipStream_t stream);
+// Gallager A/B (gb.hip), from a gb_plan of the same call: a decode of the words' bit 0 (hard, its:
+// either may be nullptr), and the fused BSC channel + decode that fills trial and trial_its.
+hipError_t launch_gb_decode(const GbPlan &p, const ldpc_graph &g, const uint8_t *d_bits, int B, int max_iters, int b,
+                            bool early_stop, uint8_t *d_hard, int32_t *d_its, hipStream_t stream);
+hipError_t launch_mc_gb(const GbPlan &p, const ldpc_graph &g, const ChanArgs &ch, uint64_t first_cw, int B,
+                        int max_iters, int b, bool early_stop, int32_t *trial, int32_t *trial_its, hipStream_t stream);
 
 // Buckets (= threads per workgroup) of the parallel graph sampler for n*dv
 // sockets; the permutation is in LDS (u16) when n*dv < 65536.  Must match

@@ -50,6 +50,54 @@ def bec_threshold(ens, iterations=100000, tol=1e-9, tolerance=1e-6):
     return 0.5 * (lo + hi)
 
 
+# ------------------------------------------------------- BSC, Gallager A/B
+def _gallager_step(dv, dc, b, p, x):
+    """One iteration of the Gallager A/B recursion on the (dv, dc) ensemble: x, the probability that
+    a v->c message is wrong, to the next.  q = (1 - (1 - 2x)^(dc-1)) / 2 is the error probability of
+    a c->v message; a wrong y is corrected when at least b of the dv - 1 other messages are right,
+    a right one is spoilt when at least b of them are wrong."""
+    from math import comb
+    q = 0.5 * (1.0 - (1.0 - 2.0 * x) ** (dc - 1))
+    d = dv - 1
+    fix = sum(comb(d, j) * (1.0 - q) ** j * q ** (d - j) for j in range(b, d + 1))
+    spoil = sum(comb(d, j) * q ** j * (1.0 - q) ** (d - j) for j in range(b, d + 1))
+    return p * (1.0 - fix) + (1.0 - p) * spoil
+
+
+def gallager_de(dv, dc, b, p, iters):
+    """Error probability of the v->c messages of Gallager's algorithm B with flip threshold b (b = 0:
+    algorithm A, b = dv - 1) on the BSC(p), (dv, dc)-regular ensemble: [p, x_1, .., x_iters]."""
+    b = dv - 1 if b == 0 else min(b, dv - 1)
+    out = [float(p)]
+    for _ in range(iters):
+        out.append(_gallager_step(dv, dc, b, p, out[-1]))
+    return out
+
+
+def gallager_threshold(dv, dc, b, tol=1e-11, floor=1e-12, iterations=1000000):
+    """Largest crossover probability whose recursion falls to zero, by bisection.  The recursion is
+    monotone in x, so from x_0 = p it either falls -- to zero, or to a fixed point above it where
+    the steps die out -- or does not fall at all."""
+    b = dv - 1 if b == 0 else min(b, dv - 1)
+    lo, hi = 0.0, 0.5
+    while hi - lo > tol:
+        mid = 0.5 * (lo + hi)
+        x, ok = mid, False
+        for _ in range(iterations):
+            nx = _gallager_step(dv, dc, b, mid, x)
+            if nx < floor:
+                ok = True
+                break
+            if nx >= x * (1.0 - 1e-13):  # no longer falling
+                break
+            x = nx
+        if ok:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
 # --------------------------------------------------------------- BI-AWGN GA
 _GH_X, _GH_W = np.polynomial.hermite.hermgauss(80)
 

@@ -268,6 +268,46 @@ def bp_ensemble_decode_dev(n, dv, dc, check_lookup, variable_lookup, llr, max_it
     return post, hard, its
 
 
+# ------------------------------------------------------------- Gallager A/B
+GALLAGER = "gallager"  # MonteCarlo(algo=GALLAGER): no ALGOS entry, the soft entry points never see it
+
+
+def _flip_threshold(b):
+    """The flip threshold of a Gallager A/B call: an integer 0 (Gallager A) .. 14."""
+    if isinstance(b, bool) or int(b) != b or not 0 <= int(b) <= 14:
+        raise ValueError(f"flip_threshold must be an integer 0 (Gallager A) .. 14, not {b!r}")
+    return int(b)
+
+
+def gallager_decode_dev(graph, bits, max_iters, flip_threshold=0, early_stop=False, hard=None, its=None, stream=None,
+                        want_hard=True, want_its=True):
+    """Gallager A (flip_threshold = 0) / B hard-decision decoding on the BSC, bit-exact with the
+    definition in include/ldpc_mi355x.h.  bits: uint8 [B, n] device tensor of received words (bit
+    0 of each byte is read).  Returns (hard uint8 [B, n], its int32 [B]) device tensors (None where
+    not wanted)."""
+    torch = _torch()
+    B = bits.shape[0]
+    assert bits.dtype == torch.uint8 and bits.is_contiguous() and bits.shape[1] == graph.n
+    if hard is None and want_hard:
+        hard = torch.empty_like(bits)
+    if its is None and want_its:
+        its = torch.empty((B,), dtype=torch.int32, device=bits.device)
+    rc = _native.lib().ldpc_gb_decode_batch_dev(graph.handle(), bits.data_ptr(), B, int(max_iters),
+                                                int(flip_threshold), int(bool(early_stop)), _ptr(hard), _ptr(its),
+                                                _stream(stream))
+    _native.check(rc, "ldpc_gb_decode_batch_dev")
+    return hard, its
+
+
+def gallager_decode(graph, bits, max_iters, flip_threshold=0, early_stop=False):
+    """Host form: bits uint8 [B, n] numpy.  Returns (hard, its) numpy."""
+    torch = _torch()
+    t = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(bits), dtype=np.uint8)).cuda()
+    hard, its = gallager_decode_dev(graph, t, max_iters, flip_threshold, early_stop)
+    torch.cuda.synchronize()
+    return hard.cpu().numpy(), its.cpu().numpy()
+
+
 # ------------------------------------------------------------------ channels
 def channel_dev(kind, param, seed, first_cw, n, B, out=None, stream=None, device=None):
     """Channel outputs of the all-zero codeword for codewords first_cw..first_cw+B-1:

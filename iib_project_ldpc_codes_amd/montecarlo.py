@@ -21,7 +21,7 @@ import time
 import numpy as np
 
 from . import _native
-from .decoder import ALGOS, CHANNELS, _quant, _schedule
+from .decoder import ALGOS, CHANNELS, GALLAGER, _flip_threshold, _quant, _schedule
 
 
 def device_executor(mc):
@@ -48,6 +48,19 @@ def device_executor(mc):
                                            mc.expurgation, int(stop_frame_errors), counters.data_ptr(),
                                            s.cuda_stream)
         _native.check(rc, entry)
+    return run
+
+
+def gallager_executor(mc):
+    """Batch executor of algo="gallager": ldpc_mc_gb_batch_dev (Gallager A/B on the BSC, bit-sliced)."""
+    torch = mc.torch
+
+    def run(first_cw, B, stop_frame_errors, counters, stream=None):
+        s = stream if stream is not None else torch.cuda.current_stream()
+        rc = _native.lib().ldpc_mc_gb_batch_dev(mc.graph.handle(), mc.param, mc.seed, int(first_cw), int(B),
+                                                mc.max_iters, mc.flip_threshold, int(mc.early_stop), mc.expurgation,
+                                                int(stop_frame_errors), counters.data_ptr(), s.cuda_stream)
+        _native.check(rc, "ldpc_mc_gb_batch_dev")
     return run
 
 
@@ -111,16 +124,29 @@ class MonteCarlo:
     schedule="layered": the row-serial schedule (decoder.bp_decode_dev) on a fixed code, BSC and
     BI-AWGN, on one rank or sharded; ensemble runs and the ML modes are flooding-only.
     quant=decoder.Quant(...) with schedule="layered" and algo="minsum": the fixed-point layered
-    min-sum (alpha is not read)."""
+    min-sum (alpha is not read).
+    algo="gallager": Gallager A (flip_threshold = 0) / B hard-decision decoding of a fixed code on the
+    BSC (decoder.gallager_decode_dev), on one rank or sharded; alpha is not read."""
 
     def __init__(self, graph, channel, param, max_iters, algo="spa", alpha=1.0, early_stop=True,
                  expurgation=-1, seed=0, batch=4096, process_group=None, executor=None, device=None,
-                 optimal=False, message_passing=True, schedule="flooding", quant=None):
+                 optimal=False, message_passing=True, schedule="flooding", quant=None, flip_threshold=0):
         import torch
         self.torch = torch
         self.graph = graph
         self.channel = CHANNELS[channel]
         self.schedule = _schedule(schedule)
+        self.gallager = algo == GALLAGER
+        if self.gallager:
+            if self.channel != CHANNELS["bsc"]:
+                raise ValueError('algo="gallager" decodes the BSC only')
+            if isinstance(graph, _Ensemble):
+                raise ValueError('algo="gallager" needs a fixed code (no ensemble form)')
+            if self.schedule == "layered" or quant is not None or optimal:
+                raise ValueError('algo="gallager" has one schedule and one-bit messages: no layered, quant or ML mode')
+            self.flip_threshold = _flip_threshold(flip_threshold)
+        elif flip_threshold:
+            raise ValueError('flip_threshold belongs to algo="gallager"')
         if self.schedule == "layered":
             if isinstance(graph, _Ensemble):
                 raise ValueError("the layered schedule needs a fixed code: no host-built schedule per sampled graph")
@@ -128,8 +154,8 @@ class MonteCarlo:
                 raise ValueError("the layered schedule decodes the BSC and the BI-AWGN channel (no BEC / ML modes)")
         self.param = float(param)
         self.max_iters = int(max_iters)
-        self.algo = ALGOS[algo]
-        self.quant = _quant(quant, self.schedule, algo)
+        self.algo = GALLAGER if self.gallager else ALGOS[algo]
+        self.quant = None if self.gallager else _quant(quant, self.schedule, algo)
         self.alpha = float(alpha)
         self.early_stop = bool(early_stop)
         self.expurgation = int(expurgation)
@@ -153,6 +179,8 @@ class MonteCarlo:
         if executor is None:
             if self.optimal:
                 executor = ml_executor(self)
+            elif self.gallager:
+                executor = gallager_executor(self)
             elif isinstance(graph, _Ensemble):
                 executor = ensemble_executor(self, graph.n, graph.dv, graph.dc)
             else:

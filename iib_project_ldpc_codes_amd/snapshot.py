@@ -61,13 +61,15 @@ def graph_fingerprint(graph):
 
 def config(mc):
     cfg = {"graph": graph_fingerprint(mc.graph), "channel": int(mc.channel), "param": float(mc.param),
-           "max_iters": int(mc.max_iters), "algo": int(mc.algo), "alpha": float(mc.alpha),
+           "max_iters": int(mc.max_iters), "algo": 0 if getattr(mc, "gallager", False) else int(mc.algo), "alpha": float(mc.alpha),
            "early_stop": bool(mc.early_stop), "expurgation": int(mc.expurgation),
            "optimal": bool(mc.optimal), "message_passing": bool(mc.message_passing)}
     if getattr(mc, "schedule", "flooding") == "layered":  # flooding snapshots stay as they always were
         cfg.update({"schedule": "layered", "layer_rule": LAYER_RULE})
     if getattr(mc, "quant", None) is not None:  # the fixed-point decoder: only then, so every other config is unchanged
         cfg["quant"] = mc.quant.as_dict()
+    if getattr(mc, "gallager", False):  # Gallager A/B: only then, as above (alpha is not read: recorded as it was given)
+        cfg.update({"algo": "gallager", "flip_threshold": int(mc.flip_threshold)})
     return cfg
 
 

@@ -189,6 +189,58 @@ int ldpc_mc_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t se
                       int64_t stop_frame_errors, int64_t *d_counters, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Gallager A/B: hard-decision decoding on the BSC (csrc/gb.hip)           */
+/* ---------------------------------------------------------------------- */
+/*
+ * Gallager's algorithm A/B, the BSC sibling of message_passing.c: one-bit
+ * messages, bit-sliced on the device (a workgroup decodes a plane word of
+ * codewords per instruction).  Every value is an integer: the kernels are
+ * bit-exact with the text below (tests/gallager_ref.py restates it).
+ *
+ * Graph: any consistent graph of ldpc_graph_create / ldpc_graph_create_csr,
+ * taken slot by slot.  A check that holds a variable twice simply has two slots.
+ * The received word is y in {0,1}^n.  There is one bit per edge and direction.
+ * The parameter is b (flip threshold), 0 <= b <= 14.
+ *
+ * For a variable of degree d, the threshold b_d is:
+ *   b = 0:  b_d = d - 1 (Gallager A: all the others must disagree).
+ *   b >= 1: b_d = min(b, d - 1) (Gallager B).
+ *   A variable of degree 1 always sends y_v.
+ *
+ *   m_vc(e) = y_v for every edge e = (v, c)
+ *   iteration t = 1..max_iters:
+ *     check c:     m_cv(e_j) = XOR_{k != j} m_vc(e_k)                    (all slots of c)
+ *     variable v:  dis_j = m_cv(e_j) ^ y_v,  D = sum_j dis_j             (all d edges of v)
+ *                  x_v   = y_v ^ [2 D > d + 1]                           (majority of the d messages and y; a tie keeps y)
+ *                  m_vc(e_j) = y_v ^ [D - dis_j >= b_d]   (d >= 2; d = 1: y_v)
+ *     early_stop: x satisfies every check -> stop, its = t
+ *   hard = x of the last iteration run (max_iters = 0: hard = y, its = 0); without early stop its = max_iters
+ *
+ * Monte-Carlo uses the all-zero codeword through the BSC stream of
+ * ldpc_channel_dev: y_v of trial t is 1 exactly where that stream's LLR is
+ * negative.  curve[0] = weight of y, curve[t] = weight of x after iteration t;
+ * the tail repeats the stopping iteration's count.  Counters, expurgation and the
+ * sequential stop rule are ldpc_mc_batch_dev's; trial index and seed are used in
+ * full 64-bit width.
+ *
+ * Limits: variable degrees <= 15 (the disagreement count is four bit planes),
+ * anything larger returns LDPC_EUNSUP; check degree is unbounded.  b outside
+ * 0..14, a NULL graph, B < 0 or max_iters < 0 returns LDPC_EINVAL.  If the planes
+ * of the graph (one word per slot and per variable, a second per variable under
+ * early stop or Monte-Carlo) do not fit LDS at the narrowest plane word (u8), the
+ * call returns LDPC_EUNSUP: there is no slab form.
+ *
+ * d_bits uint8[B*n]: only bit 0 of each byte is read.  d_hard uint8[B*n] and
+ * d_its int32[B] may each be NULL.  Both entries are asynchronous on `stream`.
+ */
+int ldpc_gb_decode_batch_dev(const ldpc_graph *g, const uint8_t *d_bits, int B, int max_iters, int b,
+                             int early_stop, uint8_t *d_hard, int32_t *d_its, void *stream);
+/* p: the crossover probability, in (0, 0.5).  d_counters: as ldpc_mc_batch_dev. */
+int ldpc_mc_gb_batch_dev(const ldpc_graph *g, float p, uint64_t seed, uint64_t first_cw, int B, int max_iters,
+                         int b, int early_stop, int expurgation, int64_t stop_frame_errors,
+                         int64_t *d_counters, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* Layered (row-serial) schedule on a fixed code (csrc/bp_layer.hip)       */
 /* ---------------------------------------------------------------------- */
 /*
@@ -555,6 +607,18 @@ int ldpc_quant_check(const ldpc_quant *q);
  * bec_peel_kernel<1024> or none.
  */
 int ldpc_debug_bec_plan(int n, int m, int dc, int count, const int32_t *calls, int64_t *out, char *names);
+
+/*
+ * Host-only: the launch plans of `count` Gallager A/B calls on a graph of n variables and E
+ * slots (csrc/gb_plan.cpp gb_plan), from the shape alone.  calls[i] = {B, iters, early_stop, mc}:
+ * mc 0 ldpc_gb_decode_batch_dev, 1 ldpc_mc_gb_batch_dev.  out[i] int64[8] = {threads, W, plane
+ * bytes, codewords per workgroup, grid, dynamic LDS bytes, LDS cap, scratch bytes}: W plane
+ * words per slot (1) of plane bytes each (4: u32, 2: u16, 1: u8); grid = ceil(B / codewords per
+ * workgroup); scratch: the Monte-Carlo trial rows and iteration counts, 0 for a decode.  A call
+ * whose planes fit LDS at no plane word (the entry returns LDPC_EUNSUP) is a row of zeros.
+ * names + 64 i: the display name, gb_kernel<T,u32|u16|u8[,es][,mc]> or none.
+ */
+int ldpc_debug_gb_plan(int n, int E, int count, const int32_t *calls, int64_t *out, char *names);
 
 /*
  * Host-only: the launch plan of one graph-sampler call (csrc/sample_plan.cpp sample_plan), from

@@ -11,6 +11,8 @@
 (decoder.bp_decode_dev; the ensemble has no layered form).
 --quant bits,post_bits,scale,norm8,offset (cfg3 with --schedule layered): the fixed-point layered
 min-sum (decoder.Quant) -- what frame error rate a q-bit hardware decoder reaches.
+--algo gallager [--flip-threshold b] (cfg3): Gallager A (b = 0) / B hard-decision decoding on the same
+code and crossover points (decoder.gallager_decode_dev), to set beside min-sum.
 One process per GPU: `--gpus N` starts the N ranks itself (decided before any HIP call, refused
 when fewer than N GPUs are visible -- iib_project_ldpc_codes_amd/launch.py, the same plan as
 bench.py), or runs as a rank of an external torchrun; trials shard by index, counters are
@@ -22,6 +24,7 @@ parallel_simulator.py:198), --trials, or --seconds.
   python scripts/fer_sweep.py ens --channel bsc --algo minsum --points 0.07,0.065
   python scripts/fer_sweep.py cfg3 --schedule layered --points 0.07
   python scripts/fer_sweep.py cfg3 --schedule layered --quant 5,7,2.0,6,0 --points 0.07
+  python scripts/fer_sweep.py cfg3 --algo gallager --points 0.038,0.035,0.03
 """
 import argparse
 import json
@@ -67,8 +70,10 @@ def parse(argv=None):
     ap.add_argument("--expurgation", type=int, default=None,
                     help="ens: X (parallel_simulator_expurgated.py argv[9]); default 3 on the BEC, none otherwise")
     ap.add_argument("--channel", choices=["bec", "bsc", "awgn"], default="bec", help="ens: the channel")
-    ap.add_argument("--algo", choices=["spa", "minsum"], default=None,
-                    help="ens on bsc / awgn: the decoder (default minsum on bsc, spa on awgn)")
+    ap.add_argument("--algo", choices=["spa", "minsum", "gallager"], default=None,
+                    help="ens on bsc / awgn: the decoder (default minsum on bsc, spa on awgn); cfg3: gallager")
+    ap.add_argument("--flip-threshold", type=int, default=0,
+                    help="cfg3 with --algo gallager: b (0: Gallager A, 1..14: Gallager B)")
     ap.add_argument("--schedule", choices=["flooding", "layered"], default="flooding",
                     help="cfg3 / cfg4: the decoding schedule (layered: row-serial, about half the iterations)")
     ap.add_argument("--quant", type=parse_quant, default=None, metavar="BITS,POST_BITS,SCALE,NORM8,OFFSET",
@@ -87,6 +92,10 @@ def parse(argv=None):
         ap.error("--schedule layered needs a fixed code (cfg3, cfg4): no host-built schedule per sampled graph")
     if args.quant is not None and (args.schedule != "layered" or args.config != "cfg3"):
         ap.error("--quant needs cfg3 (min-sum) with --schedule layered")
+    if args.algo == "gallager" and (args.config != "cfg3" or args.schedule != "flooding"):
+        ap.error("--algo gallager needs cfg3 with the flooding schedule (a fixed code on the BSC)")
+    if args.flip_threshold and args.algo != "gallager":
+        ap.error("--flip-threshold belongs to --algo gallager")
     return args
 
 
@@ -110,6 +119,9 @@ def main(argv=None):
         channel, algo, alpha, iters = "bsc", "minsum", 0.75, 50
         points = [float(p) for p in (args.points or "0.07,0.065,0.06,0.055,0.05").split(",")]
         batch = args.batch or 65536
+        if args.algo == "gallager":  # below the Gallager A threshold 0.0395 (de.gallager_threshold)
+            algo = "gallager"
+            points = [float(p) for p in (args.points or "0.038,0.036,0.034,0.032,0.03").split(",")]
     elif args.config == "ens":
         g = None
         channel = args.channel
@@ -133,7 +145,7 @@ def main(argv=None):
                                      expurgation=args.expurgation, seed=args.seed, batch=batch)
         else:
             mc = MonteCarlo(g, channel, p, iters, algo=algo, alpha=alpha, early_stop=True, seed=args.seed,
-                            batch=batch, schedule=args.schedule, quant=args.quant)
+                            batch=batch, schedule=args.schedule, quant=args.quant, flip_threshold=args.flip_threshold)
         ck = None
         if args.checkpoint_dir:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
@@ -141,6 +153,8 @@ def main(argv=None):
             if args.quant is not None:
                 q = args.quant
                 tag += "_q%d-%d-%g-%d-%d" % (q.bits, q.post_bits, q.scale, q.norm8, q.offset)
+            if algo == "gallager":
+                tag += "_gallager-b%d" % args.flip_threshold
             ck = os.path.join(args.checkpoint_dir, f"{args.config}{tag}_p={p}_seed={args.seed}_B={batch}.json")
             if os.path.exists(ck):
                 mc.restore(snapshot.load(ck))
@@ -160,6 +174,8 @@ def main(argv=None):
                 out["schedule"] = args.schedule
             if args.quant is not None:
                 out["quant"] = args.quant.as_dict()
+            if algo == "gallager":
+                out["flip_threshold"] = args.flip_threshold
             if channel == "awgn":
                 out["ebn0_db"] = float(de.sigma_to_ebn0_db(p, rate))
             print(json.dumps(out), flush=True)
