@@ -95,6 +95,17 @@ SIGNATURES = {
     "ldpc_gb_decode_batch_dev": ([P, P, i, i, i, i, P, P, P], i),
     "ldpc_mc_gb_batch_dev": ([P, f, u64, u64, i, i, i, i, i, i64, P, P], i),
     "ldpc_debug_gb_plan": ([i, i, i, P, P, P], i),
+    "ldpc_encoder_create": ([P, ct.POINTER(P)], i),
+    "ldpc_encoder_destroy": ([P], None),
+    "ldpc_encoder_info": ([P, P, P, P], i),
+    "ldpc_encoder_positions": ([P, P, P], i),
+    "ldpc_encode_rule": ([], ct.c_char_p),
+    "ldpc_debug_encoder_build": ([P, P, i, i, P, P, P, P], i),
+    "ldpc_debug_encode_plan": ([i, P, P, P], i),
+    "ldpc_encode_batch_dev": ([P, P, i, P, P], i),
+    "ldpc_info_bits_dev": ([u64, u64, i, i, P, P], i),
+    "ldpc_channel_cw_dev": ([i, f, u64, u64, i, i, P, P, P], i),
+    "ldpc_mc_cw_count_dev": ([P, P, i, P, P, i, i, i, i, i64, P, P], i),
     "ldpc_debug_sample_plan": ([i, i, i, i, i, i, i, i, i, P, P], i),
     "ldpc_sample_csr_dev": ([i, i, P, P, u64, u64, i, P, P, P, P], i),
     "ldpc_sample_csr": ([i, i, P, P, u64, u64, i, P, P, P], i),

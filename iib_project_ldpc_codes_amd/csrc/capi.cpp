@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "encode_host.hpp"
 #include "graph_device.hpp"
 #include "workspace.hpp"
 
@@ -1054,6 +1055,162 @@ int ldpc_mc_ml_batch_dev(const ldpc_graph *g, int n, int dv, int dc, float eps, 
         // ML only: the stop rule counts ML frame errors (:240-241)
         LDPC_HIP(launch_mc_reduce(du, nullptr, B, 0, -1, stop_frame_errors, d_counters_ml, cut, s));
     }
+    return LDPC_OK;
+}
+
+// --------------------------- codewords: encoder, info bits, channel, counts (encode.hip) ----------
+// The handle of a description: the two tables on the current device, the positions kept on the host
+static int device_encoder(const EncoderDesc &d, ldpc_encoder **out) {
+    std::vector<uint32_t> At;
+    std::vector<int32_t> src;
+    encoder_device_tables(d, At, src);
+    std::unique_ptr<ldpc_encoder, void (*)(ldpc_encoder *)> e(new ldpc_encoder(), ldpc_encoder_destroy);
+    e->n = d.n, e->K = d.K, e->rank = d.rank, e->KW = d.KW;
+    e->info_pos = d.info_pos, e->par_pos = d.par_pos;
+    (void)hipGetDevice(&e->device);
+    if (!At.empty()) {
+        LDPC_HIP(hipMalloc(reinterpret_cast<void **>(&e->At), At.size() * 4));
+        LDPC_HIP(hipMemcpy(e->At, At.data(), At.size() * 4, hipMemcpyHostToDevice));
+    }
+    LDPC_HIP(hipMalloc(reinterpret_cast<void **>(&e->src), src.size() * 4));
+    LDPC_HIP(hipMemcpy(e->src, src.data(), src.size() * 4, hipMemcpyHostToDevice));
+    *out = e.release();
+    return LDPC_OK;
+}
+
+int ldpc_encoder_create(const ldpc_graph *g, ldpc_encoder **out) {
+    LDPC_REQUIRE(g && out, "null graph / output handle");
+    LDPC_TRY(require_device());
+    HostGraph h;  // the slots of H, back from the device graph: all the elimination reads
+    h.n = g->n, h.m = g->m;
+    h.cptr.resize((size_t)g->m + 1);
+    h.cvar.resize(g->E);
+    LDPC_HIP(hipMemcpy(h.cptr.data(), g->cptr, h.cptr.size() * 4, hipMemcpyDeviceToHost));
+    if (g->E) LDPC_HIP(hipMemcpy(h.cvar.data(), g->cvar, h.cvar.size() * 4, hipMemcpyDeviceToHost));
+    EncoderDesc d;
+    build_encoder(h, d);
+    return device_encoder(d, out);
+}
+
+void ldpc_encoder_destroy(ldpc_encoder *e) {
+    if (!e) return;
+    (void)hipFree(e->At);
+    (void)hipFree(e->src);
+    delete e;
+}
+
+int ldpc_encoder_info(const ldpc_encoder *e, int32_t *n, int32_t *K, int32_t *rank) {
+    LDPC_REQUIRE(e, "null encoder");
+    if (n) *n = e->n;
+    if (K) *K = e->K;
+    if (rank) *rank = e->rank;
+    return LDPC_OK;
+}
+
+int ldpc_encoder_positions(const ldpc_encoder *e, int32_t *info_pos, int32_t *par_pos) {
+    LDPC_REQUIRE(e, "null encoder");
+    if (info_pos) std::copy(e->info_pos.begin(), e->info_pos.end(), info_pos);
+    if (par_pos) std::copy(e->par_pos.begin(), e->par_pos.end(), par_pos);
+    return LDPC_OK;
+}
+
+const char *ldpc_encode_rule(void) { return kEncodeRule; }
+
+int ldpc_debug_encoder_build(const int32_t *check_ptr, const int32_t *check_var, int n, int m, int32_t *rank,
+                             int32_t *info_pos, int32_t *par_pos, uint32_t *A_words) {
+    LDPC_REQUIRE(check_ptr && n > 0 && m > 0 && rank, "bad encoder arguments");
+    LDPC_REQUIRE(check_ptr[0] == 0, "check_ptr must start at 0");
+    for (int c = 0; c < m; ++c) LDPC_REQUIRE(check_ptr[c + 1] >= check_ptr[c], "check_ptr must not decrease");
+    const int E = check_ptr[m];
+    LDPC_REQUIRE(E == 0 || check_var, "null check_var");
+    for (int s = 0; s < E; ++s) LDPC_REQUIRE(check_var[s] >= 0 && check_var[s] < n, "check_var outside [0, n)");
+    HostGraph h;
+    h.n = n, h.m = m;
+    h.cptr.assign(check_ptr, check_ptr + m + 1);
+    h.cvar.assign(check_var, check_var + E);
+    EncoderDesc d;
+    build_encoder(h, d);
+    *rank = d.rank;
+    if (info_pos) std::copy(d.info_pos.begin(), d.info_pos.end(), info_pos);
+    if (par_pos) std::copy(d.par_pos.begin(), d.par_pos.end(), par_pos);
+    if (A_words) std::copy(d.A.begin(), d.A.end(), A_words);
+    return LDPC_OK;
+}
+
+// The launch plans (encode_plan) of `count` encode calls, from the shape alone.  calls[i] = {n, K,
+// rank, B}; out + 9 i = {threads, W, codewords per workgroup, grid, LDS bytes, LDS cap, plane words
+// per parity row, scratch bytes, grid of the write pass}; names + 64 i: the kernel's display name.
+// LDPC_EUNSUP, after every row is filled, when some call's information planes fit LDS at no W (its
+// row: zeros named "none").
+int ldpc_debug_encode_plan(int count, const int32_t *calls, int64_t *out, char *names) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)), "bad plan arguments");
+    bool none = false;
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 4 * (size_t)i;
+        LDPC_REQUIRE(c[0] > 0 && c[1] >= 0 && c[2] >= 0 && c[1] + c[2] == c[0] && c[3] >= 0, "bad plan arguments");
+        const EncodePlan p = encode_plan(c[0], c[1], c[2], c[3]);
+        int64_t *o = out + 9 * (size_t)i;
+        o[0] = p.threads; o[1] = p.W; o[2] = p.cw_per_wg; o[3] = p.grid; o[4] = (int64_t)p.lds; o[5] = (int64_t)p.cap;
+        o[6] = p.pwords; o[7] = (int64_t)p.scratch; o[8] = p.write_grid;
+        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+        none |= !p.threads;
+    }
+    if (none) {
+        set_error("the information planes (4 K bytes per 32 codewords) fit LDS at no tile width");
+        return LDPC_EUNSUP;
+    }
+    return LDPC_OK;
+}
+
+int ldpc_encode_batch_dev(const ldpc_encoder *e, const uint8_t *d_info, int B, uint8_t *d_cw, void *stream) {
+    LDPC_REQUIRE(e && B >= 0, "bad encode arguments");
+    LDPC_REQUIRE(B == 0 || (d_cw && (d_info || e->K == 0)), "null information bits / codewords");
+    if (B == 0) return LDPC_OK;
+    const EncodePlan p = encode_plan(e->n, e->K, e->rank, B);
+    if (!p.threads) {
+        set_error("the information planes (4 K bytes per 32 codewords) fit LDS at no tile width");
+        return LDPC_EUNSUP;
+    }
+    LDPC_REQUIRE(p.write_grid <= 0x7fffffff, "B * n beyond one launch: encode in smaller batches");
+    std::lock_guard<std::mutex> lk(g_mu);
+    Workspace &ws = workspace(stream);
+    std::lock_guard<std::mutex> wl(ws.mu);
+    uint32_t *planes = ws.scratch.get<uint32_t>(p.scratch / 4);
+    LDPC_ALLOCATED(planes);
+    LDPC_HIP(launch_encode(p, *e, d_info, B, planes, d_cw, static_cast<hipStream_t>(stream)));
+    return LDPC_OK;
+}
+
+int ldpc_info_bits_dev(uint64_t seed, uint64_t first_cw, int K, int B, uint8_t *d_info, void *stream) {
+    LDPC_REQUIRE(K >= 0 && B >= 0 && (B == 0 || K == 0 || d_info), "bad information-bit arguments");
+    LDPC_REQUIRE(((int64_t)B * ((K + 3) / 4) + 255) / 256 <= 0x7fffffff, "B * K beyond one launch");
+    LDPC_HIP(launch_info_bits(seed, first_cw, K, B, d_info, static_cast<hipStream_t>(stream)));
+    return LDPC_OK;
+}
+
+int ldpc_channel_cw_dev(int channel, float param, uint64_t seed, uint64_t first_cw, int n, int B, const uint8_t *d_cw,
+                        void *d_out, void *stream) {
+    LDPC_REQUIRE((B == 0 || d_out) && n > 0 && B >= 0, "bad channel arguments");
+    float p, p2;
+    LDPC_TRY(channel_params(channel, param, &p, &p2));
+    if (B == 0) return LDPC_OK;
+    LDPC_HIP(launch_channel_cw(channel, p, p2, seed, first_cw, n, B, d_cw, d_out, static_cast<hipStream_t>(stream)));
+    return LDPC_OK;
+}
+
+int ldpc_mc_cw_count_dev(const uint8_t *d_cw, const void *d_chan, int chan_is_llr, const uint8_t *d_hard,
+                         const int32_t *d_its, int n, int B, int max_iters, int expurgation, int64_t stop_frame_errors,
+                         int64_t *d_counters, void *stream) {
+    LDPC_REQUIRE(d_counters && n > 0 && B >= 0 && max_iters >= 0, "bad MC arguments");
+    LDPC_REQUIRE(B == 0 || (d_cw && d_chan && d_hard), "null codewords / channel outputs / decisions");
+    if (B == 0) return LDPC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only, as mc_entry
+    std::lock_guard<std::mutex> wl(ws.mu);
+    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *cut = ws.cutoff.get<int32_t>(4);
+    LDPC_ALLOCATED(trial && cut);
+    LDPC_HIP(launch_cw_count(d_cw, d_chan, chan_is_llr != 0, d_hard, n, B, max_iters, trial, s));
+    LDPC_HIP(launch_mc_reduce(trial, d_its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
     return LDPC_OK;
 }
 

@@ -407,6 +407,53 @@ hipError_t launch_gb_decode(const GbPlan &p, const ldpc_graph &g, const uint8_t 
 hipError_t launch_mc_gb(const GbPlan &p, const ldpc_graph &g, const ChanArgs &ch, uint64_t first_cw, int B,
                         int max_iters, int b, bool early_stop, int32_t *trial, int32_t *trial_its, hipStream_t stream);
 
+// The launch plan of one encode call (encode_plan.cpp): encode_parity_kernel's tile width, grid
+// and LDS and the parity-plane scratch, decided in one host-only function; encode.hip launches what
+// it says.  One workgroup encodes a tile of 32 W codewords from the tile's K information planes in
+// LDS (4 K W bytes); W is the widest of 4, 2, 1 whose planes fit kEncLdsCap.  threads == 0: they fit
+// at no W.  A workgroup past half the CU's LDS is alone on its CU and takes 1,024 threads.
+constexpr size_t kEncLdsCap = kLdsMax - 4096;
+struct EncodePlan {
+    const char *name = "none";  // display name, e.g. encode_parity_kernel<4>
+    int threads = 0;
+    int W = 0;               // plane words (of 32 codewords) per workgroup
+    int cw_per_wg = 0;       // 32 W
+    int64_t grid = 0;        // tiles: ceil(B / cw_per_wg)
+    size_t lds = 0;          // dynamic LDS bytes
+    size_t cap = 0;          // the cap `lds` was admitted under (kEncLdsCap)
+    int64_t pwords = 0;      // plane words of a parity row: grid * W
+    size_t scratch = 0;      // bytes of the parity planes uint32 [pwords][rank]
+    int64_t write_grid = 0;  // workgroups (256 threads) of encode_write_kernel: one thread per 4 variables of a codeword
+};
+EncodePlan encode_plan(int n, int K, int rank, int B);
+
+}  // namespace ldpc
+
+// Device-resident systematic encoder (encode_host.hpp's description, uploaded): the handle of the
+// C ABI's ldpc_encoder_* entries.
+struct ldpc_encoder {
+    int n = 0, K = 0, rank = 0, KW = 0, device = 0;
+    std::vector<int32_t> info_pos, par_pos;  // host copies (ldpc_encoder_positions)
+    uint32_t *At = nullptr;                  // [KW][rank] A transposed (encoder_device_tables)
+    int32_t *src = nullptr;                  // [n] information index j, or ~i of parity row i
+};
+
+namespace ldpc {
+
+// The codeword family (encode.hip).  All asynchronous on `stream`.
+// launch_encode: parity planes into `planes` (p.scratch bytes), then the codewords uint8 [B][n].
+hipError_t launch_encode(const EncodePlan &p, const ldpc_encoder &e, const uint8_t *d_info, int B, uint32_t *planes,
+                         uint8_t *d_cw, hipStream_t stream);
+// Information bits uint8 [B][K] of trials first_cw .. first_cw + B - 1 (the header's info stream)
+hipError_t launch_info_bits(uint64_t seed, uint64_t first_cw, int K, int B, uint8_t *d_info, hipStream_t stream);
+// launch_channel's outputs reflected where the codeword bit is 1 (d_cw nullptr: all-zero)
+hipError_t launch_channel_cw(int channel, float p, float p2, uint64_t seed, uint64_t first_cw, int n, int B,
+                             const uint8_t *d_cw, void *d_out, hipStream_t stream);
+// Per-trial rows for launch_mc_reduce: trial[b][0] = channel errors, trial[b][max_iters] = final
+// errors against the codeword, the entries between them 0.
+hipError_t launch_cw_count(const uint8_t *d_cw, const void *d_chan, bool chan_is_llr, const uint8_t *d_hard, int n,
+                           int B, int max_iters, int32_t *trial, hipStream_t stream);
+
 // Buckets (= threads per workgroup) of the parallel graph sampler for n*dv
 // sockets; the permutation is in LDS (u16) when n*dv < 65536.  Must match
 // oracle_sample_regular.

@@ -64,6 +64,54 @@ def gallager_executor(mc):
     return run
 
 
+def codeword_executor(mc):
+    """Batch executor of codewords="random": the unfused chain information bits (ldpc_info_bits_dev) ->
+    encode (ldpc_encode_batch_dev) -> codeword channel (ldpc_channel_cw_dev) -> the configured decoder's
+    device decode entry -> counts against the codeword (ldpc_mc_cw_count_dev).  The soft decoders are
+    asked for hard decisions only, so an early-stop decode of a fixed code stays on the local-edge
+    kernel; Gallager's received bits are llr < 0.  Buffers are kept per batch size."""
+    from . import decoder
+    from .encoder import Encoder
+    torch = mc.torch
+    enc = getattr(mc.graph, "_encoder", None)  # one elimination per graph object, whatever runs share it
+    if enc is None:
+        enc = mc.graph._encoder = Encoder(mc.graph)
+    mc.encoder = enc
+    n, K = mc.graph.n, enc.K
+    bufs = {}
+
+    def run(first_cw, B, stop_frame_errors, counters, stream=None):
+        B = int(B)
+        if B <= 0:
+            return
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if B not in bufs:
+            u8 = dict(dtype=torch.uint8, device=counters.device)
+            bufs[B] = (torch.empty((B, K), **u8), torch.empty((B, n), **u8),
+                       torch.empty((B, n), dtype=torch.float32, device=counters.device), torch.empty((B, n), **u8),
+                       torch.empty((B,), dtype=torch.int32, device=counters.device))
+        info, cw, llr, hard, its = bufs[B]
+        with torch.cuda.stream(s):
+            enc.info_bits_dev(mc.seed, first_cw, B, out=info, stream=s)
+            enc.encode_dev(info, out=cw, stream=s)
+            decoder.channel_dev(mc.channel, mc.param, mc.seed, first_cw, n, B, out=llr, stream=s, codewords=cw)
+            if mc.gallager:
+                bits = (llr < 0).to(torch.uint8)
+                decoder.gallager_decode_dev(mc.graph, bits, mc.max_iters, mc.flip_threshold, mc.early_stop, hard=hard,
+                                            its=its, stream=s)
+            else:
+                decoder.bp_decode_dev(mc.graph, llr, mc.max_iters, mc.algo, mc.alpha, mc.early_stop, hard=hard, its=its,
+                                      stream=s, want_post=False, schedule=mc.schedule, quant=mc.quant)
+        rc = _native.lib().ldpc_mc_cw_count_dev(cw.data_ptr(), llr.data_ptr(), 1, hard.data_ptr(), its.data_ptr(), n, B,
+                                                mc.max_iters, mc.expurgation, int(stop_frame_errors),
+                                                counters.data_ptr(), s.cuda_stream)
+        _native.check(rc, "ldpc_mc_cw_count_dev")
+    return run
+
+
+CODEWORDS = ("zero", "random")
+
+
 def ensemble_executor(mc, n, dv, dc):
     """Batch executor for ensemble mode: trial t decodes on its own random (dv, dc)
     graph t (parallel_simulator.py:198-231 draws a fresh code per trial):
@@ -126,17 +174,34 @@ class MonteCarlo:
     quant=decoder.Quant(...) with schedule="layered" and algo="minsum": the fixed-point layered
     min-sum (alpha is not read).
     algo="gallager": Gallager A (flip_threshold = 0) / B hard-decision decoding of a fixed code on the
-    BSC (decoder.gallager_decode_dev), on one rank or sharded; alpha is not read."""
+    BSC (decoder.gallager_decode_dev), on one rank or sharded; alpha is not read.
+    codewords="random": every trial transmits its own random codeword (codeword_executor) instead of
+    the all-zero one, and errors are counted against it -- the validation mode for decoders with ties
+    (a zero posterior decides 0, which the all-zero shortcut counts as correct).  Fixed codes on the
+    BSC and BI-AWGN, every decoder above; unfused, so of the curve only the two ends (channel and
+    final errors) are counted."""
 
     def __init__(self, graph, channel, param, max_iters, algo="spa", alpha=1.0, early_stop=True,
                  expurgation=-1, seed=0, batch=4096, process_group=None, executor=None, device=None,
-                 optimal=False, message_passing=True, schedule="flooding", quant=None, flip_threshold=0):
+                 optimal=False, message_passing=True, schedule="flooding", quant=None, flip_threshold=0,
+                 codewords="zero"):
         import torch
         self.torch = torch
         self.graph = graph
         self.channel = CHANNELS[channel]
         self.schedule = _schedule(schedule)
         self.gallager = algo == GALLAGER
+        if codewords not in CODEWORDS:
+            raise ValueError(f"codewords must be one of {CODEWORDS}, not {codewords!r}")
+        self.codewords = codewords
+        if codewords == "random":
+            if isinstance(graph, _Ensemble):
+                raise ValueError('codewords="random" needs a fixed code: a per-trial graph has no encoder')
+            if optimal:
+                raise ValueError('codewords="random" has no ML mode')
+            if self.channel == CHANNELS["bec"]:
+                raise ValueError('codewords="random" is for the BSC and BI-AWGN: erasure decoding does not depend '
+                                 "on the codeword")
         if self.gallager:
             if self.channel != CHANNELS["bsc"]:
                 raise ValueError('algo="gallager" decodes the BSC only')
@@ -179,6 +244,8 @@ class MonteCarlo:
         if executor is None:
             if self.optimal:
                 executor = ml_executor(self)
+            elif self.codewords == "random":
+                executor = codeword_executor(self)
             elif self.gallager:
                 executor = gallager_executor(self)
             elif isinstance(graph, _Ensemble):
@@ -336,6 +403,9 @@ class MonteCarlo:
                 return out
         trials = int(g[0])
         curve = g[_native.MC_NCOUNT:].astype(np.float64)
+        if self.codewords == "random":  # unfused: only the two ends of the curve are counted
+            curve[1:-1] = np.nan
+            out = {**out, "codewords": "random", "channel_bit_errors": int(g[_native.MC_NCOUNT])}
         return {**out,
             "num_tests": trials,
             "frame_errors": int(g[1]),

@@ -70,6 +70,8 @@ def config(mc):
         cfg["quant"] = mc.quant.as_dict()
     if getattr(mc, "gallager", False):  # Gallager A/B: only then, as above (alpha is not read: recorded as it was given)
         cfg.update({"algo": "gallager", "flip_threshold": int(mc.flip_threshold)})
+    if getattr(mc, "codewords", "zero") == "random":  # only then: all-zero snapshots stay as they always were
+        cfg["codewords"] = "random"
     return cfg
 
 

@@ -241,6 +241,97 @@ int ldpc_mc_gb_batch_dev(const ldpc_graph *g, float p, uint64_t seed, uint64_t f
                          int64_t *d_counters, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Codewords: encoder, information bits, channel, counts (csrc/encode.hip) */
+/* ---------------------------------------------------------------------- */
+/*
+ * Every fused Monte-Carlo entry above transmits the all-zero codeword.  That is
+ * exact only for a symmetric decoder that never meets a posterior of exactly
+ * zero: hard = post < 0 turns a tie into bit 0, the transmitted bit.  This family
+ * is decoder-independent: encode, transmit a codeword, count errors against it.
+ *
+ * H over GF(2): entry (c, v) is the parity of the number of slots of check c
+ * that hold v (a variable a check holds twice cancels, as in the decoders'
+ * XOR-over-slots syndrome).  rank = rank(H), K = n - rank: the code's true
+ * dimension, which can exceed n - m.  K = 0 is valid (the code is {0}); a variable
+ * in no check is an information position.
+ *
+ * The elimination (ldpc_encode_rule names it; csrc/encode_host.cpp): bit-packed
+ * Gauss-Jordan on 64-bit words, columns scanned from n - 1 downward, each pivoting
+ * on the lowest unused row that holds a 1.  par_pos[rank]: the pivot columns in
+ * pivot order (falling, so parity sits at the high end); info_pos[K]: the other
+ * columns, ascending; A: the dense rank x K bit matrix with
+ *   x[info_pos[j]] = u[j],   x[par_pos[i]] = XOR_j A[i][j] u[j],
+ * packed in uint32 words, row i at A_words + i * ceil(K / 32), bit j of the row =
+ * bit (j & 31) of word j >> 5, the padding bits zero.  Deterministic: the same
+ * graph gives the same positions and the same A.  Cost about rank^2 n / 128 word
+ * operations on the host (seconds at n = 10,000 - 20,000, minutes at n = 64,800).
+ *
+ * ldpc_encoder_create runs the elimination on the host and uploads the tables to
+ * the current device.  ldpc_debug_encoder_build is the same elimination from a
+ * CSR check side alone, host-only (no device): A_words, info_pos and par_pos may
+ * each be NULL.
+ *
+ * ldpc_encode_batch_dev: d_info uint8[B*K] (bit 0 of each byte is read; may be
+ * NULL when K = 0) -> d_cw uint8[B*n] of 0/1, P = A U over GF(2) bit-sliced
+ * (32 codewords per plane word; ldpc_debug_encode_plan).  LDPC_EUNSUP when the
+ * information planes of the narrowest tile (4 K bytes) do not fit LDS.
+ *
+ * ldpc_info_bits_dev: bit j of trial t (= first_cw + row) is bit j & 31 of word
+ * (j >> 5) & 3 of the Philox4x32-10 block with counter {j >> 7, 1, t_lo, t_hi}
+ * under the channels' key {seed_lo, seed_hi}.  Every channel's second counter
+ * word is 0, so the two streams never meet; seed and trial index are used in
+ * full 64-bit width, and trial t is the same in any batch.
+ *
+ * ldpc_channel_cw_dev: the output of ldpc_channel_dev for the same (seed, trial),
+ * reflected where the codeword bit x (bit 0 of d_cw's byte) is 1:
+ *   BEC: the same erased positions (2), otherwise x;
+ *   BSC / AWGN: llr_x = x ? -llr_0 : llr_0, an exact negation.
+ * (Physically the noise is (1 - 2x) sigma g: the same law, g being symmetric and
+ * independent of x.)  d_cw NULL = the all-zero codeword: ldpc_channel_dev's
+ * output bit for bit.  A tie-free symmetric decode of trial t is thus the exact
+ * mirror of the fused all-zero decode of trial t.
+ *
+ * ldpc_mc_cw_count_dev: per trial, channel errors = [llr < 0] != x (chan_is_llr
+ * != 0: d_chan float[B*n]; 0: d_chan uint8[B*n] of received bits, bit 0 != x) and
+ * final errors = hard != x.  d_counters has ldpc_mc_batch_dev's layout and length
+ * and is accumulated: [0]..[3] as there ([3] sums d_its, which may be NULL),
+ * curve[0] += channel errors, curve[max_iters] += final errors (max_iters = 0: the
+ * one entry takes the final errors).  The curve entries between the two ends are
+ * not touched: an unfused decode has no per-iteration view.  Expurgation and the
+ * sequential stop rule are ldpc_mc_batch_dev's, on the final errors.
+ *
+ * Errors: a NULL handle, B < 0, K < 0, n <= 0, a NULL array that is read or
+ * written (B > 0), a bad channel parameter: LDPC_EINVAL.  B = 0 is a no-op.  All
+ * four device entries are asynchronous on `stream`.
+ */
+typedef struct ldpc_encoder ldpc_encoder;
+int ldpc_encoder_create(const ldpc_graph *g, ldpc_encoder **out);
+void ldpc_encoder_destroy(ldpc_encoder *e);
+int ldpc_encoder_info(const ldpc_encoder *e, int32_t *n, int32_t *K, int32_t *rank);
+int ldpc_encoder_positions(const ldpc_encoder *e, int32_t *info_pos /* K */, int32_t *par_pos /* rank */);
+const char *ldpc_encode_rule(void);
+int ldpc_debug_encoder_build(const int32_t *check_ptr, const int32_t *check_var, int n, int m, int32_t *rank,
+                             int32_t *info_pos, int32_t *par_pos, uint32_t *A_words /* rank * ceil(K/32) */);
+int ldpc_encode_batch_dev(const ldpc_encoder *e, const uint8_t *d_info, int B, uint8_t *d_cw, void *stream);
+int ldpc_info_bits_dev(uint64_t seed, uint64_t first_cw, int K, int B, uint8_t *d_info, void *stream);
+int ldpc_channel_cw_dev(int channel, float param, uint64_t seed, uint64_t first_cw, int n, int B,
+                        const uint8_t *d_cw, void *d_out, void *stream);
+int ldpc_mc_cw_count_dev(const uint8_t *d_cw, const void *d_chan, int chan_is_llr, const uint8_t *d_hard,
+                         const int32_t *d_its, int n, int B, int max_iters, int expurgation,
+                         int64_t stop_frame_errors, int64_t *d_counters, void *stream);
+/*
+ * Host-only: the launch plans of `count` encode calls (csrc/encode_plan.cpp encode_plan), from
+ * the shape alone.  calls[i] = {n, K, rank, B} (K + rank = n).  out[i] int64[9] = {threads, W,
+ * codewords per workgroup (32 W), grid = ceil(B / (32 W)), dynamic LDS bytes (4 K W), LDS cap
+ * (160 KiB - 4 KiB), plane words per parity row (grid W), scratch bytes (4 rank grid W), workgroups
+ * of the write pass}: W is the widest of 4, 2, 1 whose planes fit the cap; 1,024 threads when the
+ * planes take more than half a CU's LDS, else 256.  A call that fits at no W is a row of zeros
+ * named "none", and the entry returns LDPC_EUNSUP after filling every row.  names + 64 i: the
+ * display name, encode_parity_kernel<W> or none.
+ */
+int ldpc_debug_encode_plan(int count, const int32_t *calls, int64_t *out, char *names);
+
+/* ---------------------------------------------------------------------- */
 /* Layered (row-serial) schedule on a fixed code (csrc/bp_layer.hip)       */
 /* ---------------------------------------------------------------------- */
 /*

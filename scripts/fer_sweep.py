@@ -13,6 +13,9 @@
 min-sum (decoder.Quant) -- what frame error rate a q-bit hardware decoder reaches.
 --algo gallager [--flip-threshold b] (cfg3): Gallager A (b = 0) / B hard-decision decoding on the same
 code and crossover points (decoder.gallager_decode_dev), to set beside min-sum.
+--codewords random (cfg3, cfg4): every trial transmits a random codeword and errors are counted
+against it (MonteCarlo codewords="random": encode, codeword channel, decode, count; unfused) -- no
+all-zero shortcut, so a decoder's ties are not counted as correct.
 One process per GPU: `--gpus N` starts the N ranks itself (decided before any HIP call, refused
 when fewer than N GPUs are visible -- iib_project_ldpc_codes_amd/launch.py, the same plan as
 bench.py), or runs as a rank of an external torchrun; trials shard by index, counters are
@@ -25,6 +28,7 @@ parallel_simulator.py:198), --trials, or --seconds.
   python scripts/fer_sweep.py cfg3 --schedule layered --points 0.07
   python scripts/fer_sweep.py cfg3 --schedule layered --quant 5,7,2.0,6,0 --points 0.07
   python scripts/fer_sweep.py cfg3 --algo gallager --points 0.038,0.035,0.03
+  python scripts/fer_sweep.py cfg3 --schedule layered --quant 5,7,2.0,8,1 --codewords random --points 0.06
 """
 import argparse
 import json
@@ -78,6 +82,9 @@ def parse(argv=None):
                     help="cfg3 / cfg4: the decoding schedule (layered: row-serial, about half the iterations)")
     ap.add_argument("--quant", type=parse_quant, default=None, metavar="BITS,POST_BITS,SCALE,NORM8,OFFSET",
                     help="cfg3 with --schedule layered: the fixed-point layered min-sum (decoder.Quant)")
+    ap.add_argument("--codewords", choices=["zero", "random"], default="zero",
+                    help="cfg3 / cfg4: random transmits a random codeword per trial and counts against it "
+                         "(MonteCarlo codewords=, the unfused validation mode)")
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks, one process per GPU (default: torchrun's WORLD_SIZE, else 1); "
                          "without WORLD_SIZE the sweep starts them itself")
@@ -96,6 +103,8 @@ def parse(argv=None):
         ap.error("--algo gallager needs cfg3 with the flooding schedule (a fixed code on the BSC)")
     if args.flip_threshold and args.algo != "gallager":
         ap.error("--flip-threshold belongs to --algo gallager")
+    if args.codewords == "random" and args.config == "ens":
+        ap.error("--codewords random needs a fixed code (cfg3, cfg4): a per-trial graph has no encoder")
     return args
 
 
@@ -145,7 +154,8 @@ def main(argv=None):
                                      expurgation=args.expurgation, seed=args.seed, batch=batch)
         else:
             mc = MonteCarlo(g, channel, p, iters, algo=algo, alpha=alpha, early_stop=True, seed=args.seed,
-                            batch=batch, schedule=args.schedule, quant=args.quant, flip_threshold=args.flip_threshold)
+                            batch=batch, schedule=args.schedule, quant=args.quant, flip_threshold=args.flip_threshold,
+                            codewords=args.codewords)
         ck = None
         if args.checkpoint_dir:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
@@ -155,6 +165,8 @@ def main(argv=None):
                 tag += "_q%d-%d-%g-%d-%d" % (q.bits, q.post_bits, q.scale, q.norm8, q.offset)
             if algo == "gallager":
                 tag += "_gallager-b%d" % args.flip_threshold
+            if args.codewords == "random":
+                tag += "_cw-random"
             ck = os.path.join(args.checkpoint_dir, f"{args.config}{tag}_p={p}_seed={args.seed}_B={batch}.json")
             if os.path.exists(ck):
                 mc.restore(snapshot.load(ck))
@@ -176,6 +188,8 @@ def main(argv=None):
                 out["quant"] = args.quant.as_dict()
             if algo == "gallager":
                 out["flip_threshold"] = args.flip_threshold
+            if args.codewords == "random":
+                out["codewords"] = "random"
             if channel == "awgn":
                 out["ebn0_db"] = float(de.sigma_to_ebn0_db(p, rate))
             print(json.dumps(out), flush=True)
