@@ -506,42 +506,32 @@ __global__ __launch_bounds__(T) void bec_dec_bits_kernel(BecArgs a, int B) {
 // 2. Launchers.  bec_plan (bec_plan.cpp) names the kernel, its shape, grid and LDS; the code
 // below fills the arguments and launches that instantiation.
 // ---------------------------------------------------------------------------
-template <typename K, typename... A>
-hipError_t launch_planned(K kernel, const BecPlan &p, hipStream_t stream, const A &...args) {
-    hipError_t e = allow_lds(kernel, p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3(p.threads), p.lds, stream, args...);
-    return hipGetLastError();
-}
-
 template <bool DEC, int T, int W, typename P>
 hipError_t launch_bits_as(const BecPlan &p, const BecArgs &a, int B, hipStream_t stream) {
-    if constexpr (DEC) return launch_planned(bec_dec_bits_kernel<T, W, P>, p, stream, a, B);
-    else return launch_planned(bec_mc_bits_kernel<T, W, P>, p, stream, a, B);
+    const dim3 grid((unsigned)p.grid), block(T);
+    if constexpr (DEC) return launch_lds(bec_dec_bits_kernel<T, W, P>, grid, block, p.lds, stream, a, B);
+    else return launch_lds(bec_mc_bits_kernel<T, W, P>, grid, block, p.lds, stream, a, B);
 }
 
-// The bit-sliced instantiations: (threads, plane words per variable, plane word).  The kernels
-// lie in the code object in the order of these cases (and Decode's before Monte-Carlo's): it is
-// kept as it was measured.
-constexpr int bits_key(int T, int W, int plane) { return T * 100 + W * 10 + plane; }
+// The bit-sliced instantiations: the rows of the shape table (kernel_shapes.hpp), from which
+// bec_plan takes the shape it names.  The kernels lie in the code object in the order of the rows
+// (and Decode's before Monte-Carlo's): it is kept as it was measured.
 template <bool DEC>
 hipError_t launch_bits(const BecPlan &p, const BecArgs &a, int B, hipStream_t stream) {
-    switch (bits_key(p.threads, p.W, p.plane)) {
-        case bits_key(1024, 1, 1): return launch_bits_as<DEC, 1024, 1, uint8_t>(p, a, B, stream);
-        case bits_key(256, 4, 4): return launch_bits_as<DEC, 256, 4, uint32_t>(p, a, B, stream);
-        case bits_key(256, 2, 4): return launch_bits_as<DEC, 256, 2, uint32_t>(p, a, B, stream);
-        case bits_key(256, 1, 4): return launch_bits_as<DEC, 256, 1, uint32_t>(p, a, B, stream);
-        case bits_key(512, 4, 4): return launch_bits_as<DEC, 512, 4, uint32_t>(p, a, B, stream);
-        case bits_key(512, 2, 4): return launch_bits_as<DEC, 512, 2, uint32_t>(p, a, B, stream);
-        case bits_key(512, 1, 4): return launch_bits_as<DEC, 512, 1, uint32_t>(p, a, B, stream);
-        default: return hipErrorInvalidValue;  // a shape the plan does not give
-    }
+#define LDPC_ROW(T, WW, P, TAG) \
+    if (p.threads == T && p.W == WW && p.plane == (int)sizeof(P)) return launch_bits_as<DEC, T, WW, P>(p, a, B, stream);
+    LDPC_BEC_BITS_SHAPES(LDPC_ROW)
+#undef LDPC_ROW
+    return hipErrorInvalidValue;  // a shape without a row: the plan gives none
 }
 
 template <bool MC>
 hipError_t launch_word(const BecPlan &p, const BecArgs &a, hipStream_t stream) {
-    return p.threads == 1024 ? launch_planned(bec_kernel<1024, MC>, p, stream, a)
-                             : launch_planned(bec_kernel<256, MC>, p, stream, a);
+#define LDPC_ROW(T) \
+    if (p.threads == T) return launch_lds(bec_kernel<T, MC>, dim3((unsigned)p.grid), dim3(T), p.lds, stream, a);
+    LDPC_BEC_WORD_SHAPES(LDPC_ROW)
+#undef LDPC_ROW
+    return hipErrorInvalidValue;
 }
 
 // MC: the fused-channel forms (bec_kernel<T, true>, bec_mc_bits_kernel).  hipErrorInvalidValue: no

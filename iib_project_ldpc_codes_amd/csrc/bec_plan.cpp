@@ -17,8 +17,6 @@
 namespace ldpc {
 namespace {
 
-constexpr size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // bec_kernel's carve (bec.hip, errs | mvc | cs): caller errors[] int32[iters] | word u8[n] | one byte per check
 size_t word_lds(int n, int m, int iters) { return pad16((size_t)iters * 4) + pad16((size_t)n) + (size_t)m; }
 
@@ -41,29 +39,17 @@ size_t peel_lds(int n, int m, int F) {
 void word_plan(BecPlan &p, int n, int m, int B, int iters) {
     const size_t lds = word_lds(n, m, iters);
     if (lds > kBecWordLdsCap) return;
+    const int T = n >= 4096 ? 1024 : 256;
+    const auto *row = shapes::find(shapes::kBecWord, [&](const shapes::BecWord &r) { return r.T == T; });
+    if (!row) return;  // not with these rules: both thread counts have their row
     p.kernel = BecKernel::Word;
-    p.threads = n >= 4096 ? 1024 : 256;
+    p.threads = T;
     p.cw_per_wg = 1;
     p.grid = B;
     p.lds = lds;
     p.cap = kBecWordLdsCap;
-    p.name = p.threads == 1024 ? "bec_kernel<1024>" : "bec_kernel<256>";
+    p.name = row->name;
 }
-
-// The shapes the rules below can give, bec.hip's instantiations (launch_bits), by display name
-struct BitsShape {
-    int T, W, plane;
-    const char *name[2];  // Decode, Mc
-};
-constexpr BitsShape kBitsShapes[] = {
-    {256, 1, 4, {"bec_dec_bits_kernel<256,1,u32>", "bec_mc_bits_kernel<256,1,u32>"}},
-    {256, 2, 4, {"bec_dec_bits_kernel<256,2,u32>", "bec_mc_bits_kernel<256,2,u32>"}},
-    {256, 4, 4, {"bec_dec_bits_kernel<256,4,u32>", "bec_mc_bits_kernel<256,4,u32>"}},
-    {512, 1, 4, {"bec_dec_bits_kernel<512,1,u32>", "bec_mc_bits_kernel<512,1,u32>"}},
-    {512, 2, 4, {"bec_dec_bits_kernel<512,2,u32>", "bec_mc_bits_kernel<512,2,u32>"}},
-    {512, 4, 4, {"bec_dec_bits_kernel<512,4,u32>", "bec_mc_bits_kernel<512,4,u32>"}},
-    {1024, 1, 1, {"bec_dec_bits_kernel<1024,1,u8>", "bec_mc_bits_kernel<1024,1,u8>"}},
-};
 
 // Plane word (u32 x W words per variable, or u8 for graphs whose u32 planes do not fit) and
 // workgroup size for this graph and batch; false when not even u8 planes fit.
@@ -86,6 +72,13 @@ bool bits_plan(BecPlan &p, int n, int m, int B, bool dec) {
         T = 1024;
         if (bits_lds(n, m, dec, W, plane) > cap) return false;
     }
+    // the instantiation: the shape table's row (kernel_shapes.hpp, what bec.hip compiles).  Every
+    // (T, W, plane) the rules above give has one; a shape without a row would be no plan
+    // (BecKernel::None), not another kernel's.
+    const auto *row = shapes::find(shapes::kBecBits, [&](const shapes::BecBits &r) {
+        return r.T == T && r.W == W && r.plane == plane;
+    });
+    if (!row) return true;
     p.kernel = dec ? BecKernel::DecBits : BecKernel::McBits;
     p.threads = T;
     p.W = W;
@@ -94,8 +87,7 @@ bool bits_plan(BecPlan &p, int n, int m, int B, bool dec) {
     p.grid = grid(W, plane);
     p.lds = bits_lds(n, m, dec, W, plane);
     p.cap = cap;
-    for (const BitsShape &s : kBitsShapes)
-        if (s.T == T && s.W == W && s.plane == plane) p.name = s.name[dec ? 0 : 1];
+    p.name = dec ? row->dec : row->mc;
     return true;
 }
 

@@ -304,10 +304,7 @@ hipError_t launch_flood_shape(const BpPlan &p, LDPC_FLOOD_ARGS a, hipStream_t s)
     constexpr int T = GMEM ? LDPC_GMEM_T : 256;
     auto k = LDPC_FLOOD_KERNEL<T, MAXDC, ALGO, ET, MC, GMEM>;
     a.lds_slots = p.lds_slots;
-    hipError_t e = allow_lds(k, p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(p.grid), dim3(T), p.lds, s, a);
-    return hipGetLastError();
+    return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a);
 }
 
 hipError_t launch_flood(const BpPlan &p, const LDPC_FLOOD_ARGS &a, int algo, bool et, bool mc, hipStream_t s,

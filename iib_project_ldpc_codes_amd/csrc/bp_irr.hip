@@ -241,11 +241,7 @@ __global__ __launch_bounds__(kIrrT) void bp_irr_kernel(BpArgs a) {
 
 template <int DC, int VPT, int ALGO, bool ET, bool MC>
 hipError_t launch_irr_shape(const BpPlan &p, const BpArgs &a, hipStream_t s) {
-    auto k = bp_irr_kernel<DC, VPT, ALGO, ET, MC>;
-    hipError_t e = allow_lds(k, p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(p.grid), dim3(kIrrT), p.lds, s, a);
-    return hipGetLastError();
+    return launch_lds(bp_irr_kernel<DC, VPT, ALGO, ET, MC>, dim3(p.grid), dim3(kIrrT), p.lds, s, a);
 }
 
 template <int ALGO, bool ET, bool MC>

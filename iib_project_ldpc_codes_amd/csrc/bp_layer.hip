@@ -223,10 +223,7 @@ hipError_t launch_layer_shape(const BpPlan &p, LayerArgs a, hipStream_t s) {
     if (p.threads != T) return hipErrorInvalidValue;
     auto k = bp_layer_kernel<T, MAXDC, ALGO, ET, MC, GMEM>;
     a.lds_slots = p.lds_slots;
-    hipError_t e = allow_lds(k, p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(p.grid), dim3(T), p.lds, s, a);
-    return hipGetLastError();
+    return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a);
 }
 
 }  // namespace

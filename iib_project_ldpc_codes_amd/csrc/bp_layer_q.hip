@@ -209,12 +209,7 @@ template <int MAXDC>
 hipError_t launch_layer_q_shape(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s) {
     constexpr int T = 256;
     if (p.threads != T) return hipErrorInvalidValue;
-    auto go = [&](auto k) {
-        const hipError_t e = allow_lds(k, p.lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(p.grid), dim3(T), p.lds, s, a);
-        return hipGetLastError();
-    };
+    auto go = [&](auto k) { return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a); };
     if (et) return mc ? go(bp_layer_q_kernel<T, MAXDC, true, true>) : go(bp_layer_q_kernel<T, MAXDC, true, false>);
     return mc ? go(bp_layer_q_kernel<T, MAXDC, false, true>) : go(bp_layer_q_kernel<T, MAXDC, false, false>);
 }

@@ -414,26 +414,18 @@ __global__ __launch_bounds__(T) void bp_lds_kernel(BpArgs a) {
     }
 }
 
-template <int VPT, int T, int ALGO, bool ET, bool MC>
-hipError_t launch_lds36_vpt(const BpPlan &p, const BpArgs &a, hipStream_t s) {
-    auto k = bp_lds_kernel<3, 6, T, VPT, ALGO, ET, MC>;
-    hipError_t e = allow_lds(k, p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(p.grid), dim3(T), p.lds, s, a);
-    return hipGetLastError();
-}
-
+// The instantiations: the rows of the shape table (kernel_shapes.hpp), from which lds_shape gives
+// the lane layout its (T, VPT)
 template <int ALGO, bool ET, bool MC>
 hipError_t launch_lds36_modes(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipStream_t s) {
     a.lane_var = g.lane_var;
     a.lane_slot = g.lane_slot;
     a.E = lds_pair_span(g.m, 6);  // message positions (lds_pair_pos), dummies after
-#define LDS36_CASE(TT, VV) \
-    if (g.lane_T == TT && g.lane_VPT == VV) return launch_lds36_vpt<VV, TT, ALGO, ET, MC>(p, a, s);
-    LDS36_CASE(256, 1) LDS36_CASE(256, 2) LDS36_CASE(256, 3) LDS36_CASE(256, 5) LDS36_CASE(256, 9)
-    LDS36_CASE(1024, 2) LDS36_CASE(1024, 3) LDS36_CASE(1024, 5) LDS36_CASE(1024, 6) LDS36_CASE(1024, 9)
-    LDS36_CASE(1024, 10) LDS36_CASE(1024, 11) LDS36_CASE(1024, 14)
-#undef LDS36_CASE
+#define LDPC_ROW(T, VPT)                      \
+    if (g.lane_T == T && g.lane_VPT == VPT) \
+        return launch_lds(bp_lds_kernel<3, 6, T, VPT, ALGO, ET, MC>, dim3(p.grid), dim3(T), p.lds, s, a);
+    LDPC_LDS36_SHAPES(LDPC_ROW)
+#undef LDPC_ROW
     return hipErrorInvalidValue;
 }
 

@@ -878,14 +878,12 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
 template <int DLO, int DHI, int D0, int D1, bool A0, bool A1, int T, int KP, int ALGO, bool ET, bool MC>
 hipError_t launch_loc_shape(const BpPlan &p, BpArgs a, hipStream_t s) {
     auto launch = [&](auto k) {
-        hipError_t e = allow_lds(k, p.lds);
-        if (e != hipSuccess) return e;
         if (p.persistent) {  // the grid pulls codewords from a counter
             a.work = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(a.scratch) + p.counter);
-            if ((e = hipMemsetAsync(a.work, 0, sizeof(uint32_t), s)) != hipSuccess) return e;
+            const hipError_t e = hipMemsetAsync(a.work, 0, sizeof(uint32_t), s);
+            if (e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL(k, dim3(p.grid), dim3(T), p.lds, s, a);
-        return hipGetLastError();
+        return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a);
     };
     if constexpr (ET && !MC) {  // early stop with posteriors: per-workgroup slabs before the counter
         if (a.post) return launch(bp_loc_kernel<DLO, DHI, D0, D1, KP, T, ALGO, A0, A1, true, false, true>);
@@ -893,18 +891,19 @@ hipError_t launch_loc_shape(const BpPlan &p, BpArgs a, hipStream_t s) {
     return launch(bp_loc_kernel<DLO, DHI, D0, D1, KP, T, ALGO, A0, A1, ET, MC>);
 }
 
+// The instantiations of a variant: its rows of the shape table (kernel_shapes.hpp), the ones
+// loc_variant admits the variant for
 template <int DLO, int DHI, int D0, int D1, bool A0, bool A1, int ALGO, bool ET, bool MC>
 hipError_t launch_loc_deg(const BpPlan &p, const BpArgs &a, int T, int KP, hipStream_t s) {
-#define LOC_SHAPE(TT, KK) \
+#define LDPC_ROW(TT, KK) \
     if (T == TT && KP == KK) return launch_loc_shape<DLO, DHI, D0, D1, A0, A1, TT, KK, ALGO, ET, MC>(p, a, s);
-    LOC_SHAPE(256, 1) LOC_SHAPE(256, 2) LOC_SHAPE(256, 3) LOC_SHAPE(256, 4)
-    LOC_SHAPE(1024, 2) LOC_SHAPE(1024, 3)
-    if constexpr (DLO != DHI) {  // 512 threads, 2 waves per SIMD: the RSU-type shape only
-        LOC_SHAPE(512, 8) LOC_SHAPE(512, 10)
-    } else {  // 512 threads, two workgroups per CU
-        LOC_SHAPE(512, 5)
+    LDPC_LOC_SHAPES(LDPC_ROW)
+    if constexpr (DLO != DHI) {
+        LDPC_LOC_RSU_SHAPES(LDPC_ROW)
+    } else {
+        LDPC_LOC_REG36_SHAPES(LDPC_ROW)
     }
-#undef LOC_SHAPE
+#undef LDPC_ROW
     return hipErrorInvalidValue;
 }
 
@@ -925,10 +924,7 @@ hipError_t launch_loc_modes(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipS
             a.loc_cls_w[0] = 0; a.loc_cls_w[1] = 8 * g.chn_Tq; a.loc_cls_w[2] = g.chn_words;
             a.loc_cls_d[0] = a.loc_cls_d[1] = 6;
             auto k = bp_loc_kernel<6, 6, 2, 2, KP, T, 0, false, false, false, false, false, kLocChainCL>;
-            const hipError_t e = allow_lds(k, p.lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k, dim3(p.grid), dim3(T), p.lds, s, a);
-            return hipGetLastError();
+            return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a);
         } else {
             return hipErrorInvalidValue;
         }

@@ -40,8 +40,6 @@
 namespace ldpc {
 namespace {
 
-constexpr size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // messages | MC: per-iteration curve (16-byte padded) | min-sum MC: syndrome bits
 size_t loc_lds_bytes(const GraphShape &g, int iters, bool mc, bool syn) {
     return pad16((size_t)std::max(g.loc_words + 64, g.n) * 4) + (mc ? curve_bytes(iters) : 0) +

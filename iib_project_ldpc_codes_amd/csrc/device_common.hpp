@@ -201,5 +201,14 @@ hipError_t allow_lds(K kernel, size_t bytes) {
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// One launch with `lds` bytes of dynamic LDS, asynchronous on `s`: hipSuccess or the launch error
+template <typename K, typename... A>
+hipError_t launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...args) {
+    const hipError_t e = allow_lds(kernel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    return hipGetLastError();
+}
+
 }  // namespace
 }  // namespace ldpc

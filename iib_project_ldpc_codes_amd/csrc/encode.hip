@@ -184,14 +184,16 @@ __global__ __launch_bounds__(256) void cw_count_kernel(const uint8_t *__restrict
     }
 }
 
-template <int W>
+// The tiles: the rows of the shape table (kernel_shapes.hpp), from which encode_plan takes the W it names
 hipError_t launch_parity(const EncodePlan &p, const ldpc_encoder &e, const uint8_t *d_info, int B, uint32_t *planes,
                          hipStream_t s) {
-    hipError_t err = allow_lds(encode_parity_kernel<W>, p.lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(encode_parity_kernel<W>, dim3((unsigned)p.grid), dim3(p.threads), p.lds, s, e.At, d_info, e.K, e.KW,
-                       e.rank, B, planes);
-    return hipGetLastError();
+#define LDPC_ROW(WW)                                                                                                  \
+    if (p.W == WW)                                                                                                    \
+        return launch_lds(encode_parity_kernel<WW>, dim3((unsigned)p.grid), dim3(p.threads), p.lds, s, e.At, d_info, \
+                          e.K, e.KW, e.rank, B, planes);
+    LDPC_ENC_TILES(LDPC_ROW)
+#undef LDPC_ROW
+    return hipErrorInvalidValue;  // a tile without a row: the plan gives none
 }
 
 }  // namespace
@@ -200,13 +202,7 @@ hipError_t launch_encode(const EncodePlan &p, const ldpc_encoder &e, const uint8
                          uint8_t *d_cw, hipStream_t stream) {
     if (B <= 0 || e.n <= 0) return hipSuccess;
     if (e.rank > 0) {
-        hipError_t err;
-        switch (p.W) {
-            case 4: err = launch_parity<4>(p, e, d_info, B, planes, stream); break;
-            case 2: err = launch_parity<2>(p, e, d_info, B, planes, stream); break;
-            case 1: err = launch_parity<1>(p, e, d_info, B, planes, stream); break;
-            default: return hipErrorInvalidValue;  // a shape the plan does not give
-        }
+        const hipError_t err = launch_parity(p, e, d_info, B, planes, stream);
         if (err != hipSuccess) return err;
     }
     const bool vec = e.n % 4 == 0 && (reinterpret_cast<uintptr_t>(d_cw) & 3) == 0;

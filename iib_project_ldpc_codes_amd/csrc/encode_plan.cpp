@@ -10,12 +10,14 @@ namespace ldpc {
 // planes fit the cap -- a wider tile reads each word of A once for more codewords.
 EncodePlan encode_plan(int n, int K, int rank, int B) {
     EncodePlan p;
-    static const char *const names[5] = {"none", "encode_parity_kernel<1>", "encode_parity_kernel<2>", "none",
-                                         "encode_parity_kernel<4>"};
     for (int W : {4, 2, 1}) {
         const size_t lds = (size_t)4 * K * W;
         if (lds > kEncLdsCap) continue;
-        p.name = names[W];
+        // the instantiation: the shape table's row (kernel_shapes.hpp, what encode.hip compiles).
+        // Every W of this ladder has one; a tile without a row would be no plan.
+        const auto *row = shapes::find(shapes::kEncTiles, [&](const shapes::EncTile &r) { return r.W == W; });
+        if (!row) break;
+        p.name = row->name;
         p.threads = lds > kLdsMax / 2 ? 1024 : 256;
         p.W = W;
         p.cw_per_wg = 32 * W;

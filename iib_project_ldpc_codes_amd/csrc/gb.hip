@@ -227,32 +227,24 @@ __global__ __launch_bounds__(T) void gb_kernel(GbArgs a) {
         }
 }
 
-template <typename K>
-hipError_t launch_planned(K kernel, const GbPlan &p, hipStream_t stream, const GbArgs &a) {
-    hipError_t e = allow_lds(kernel, p.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3(p.threads), p.lds, stream, a);
-    return hipGetLastError();
-}
-
 template <int T, typename P>
 hipError_t launch_modes(const GbPlan &p, const GbArgs &a, bool es, bool mc, hipStream_t s) {
-    if (mc) return es ? launch_planned(gb_kernel<T, P, true, true>, p, s, a) : launch_planned(gb_kernel<T, P, false, true>, p, s, a);
-    return es ? launch_planned(gb_kernel<T, P, true, false>, p, s, a) : launch_planned(gb_kernel<T, P, false, false>, p, s, a);
+    const auto go = [&](auto kernel) { return launch_lds(kernel, dim3((unsigned)p.grid), dim3(T), p.lds, s, a); };
+    if (mc) return es ? go(gb_kernel<T, P, true, true>) : go(gb_kernel<T, P, false, true>);
+    return es ? go(gb_kernel<T, P, true, false>) : go(gb_kernel<T, P, false, false>);
 }
 
-// The instantiations: gb_plan's shapes (threads, plane bytes).  The graph's tables and shape come from g.
+// The instantiations: the rows of the shape table (kernel_shapes.hpp), from which gb_plan takes the
+// shape it names.  The graph's tables and shape come from g.
 hipError_t launch_gb(const GbPlan &p, const ldpc_graph &g, GbArgs a, bool es, bool mc, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     a.cptr = g.cptr, a.cvar = g.cvar, a.vptr = g.vptr, a.vslot = g.vslot;
     a.n = g.n, a.m = g.m, a.E = g.E, a.dv = g.dv, a.dc = g.dc;
-    switch (p.threads * 10 + p.plane) {
-        case 256 * 10 + 4: return launch_modes<256, uint32_t>(p, a, es, mc, s);
-        case 1024 * 10 + 4: return launch_modes<1024, uint32_t>(p, a, es, mc, s);
-        case 1024 * 10 + 2: return launch_modes<1024, uint16_t>(p, a, es, mc, s);
-        case 1024 * 10 + 1: return launch_modes<1024, uint8_t>(p, a, es, mc, s);
-        default: return hipErrorInvalidValue;  // a shape the plan does not give
-    }
+#define LDPC_ROW(T, P, TAG) \
+    if (p.threads == T && p.plane == (int)sizeof(P)) return launch_modes<T, P>(p, a, es, mc, s);
+    LDPC_GB_SHAPES(LDPC_ROW)
+#undef LDPC_ROW
+    return hipErrorInvalidValue;  // a shape without a row: the plan gives none
 }
 
 }  // namespace

@@ -6,27 +6,12 @@
 namespace ldpc {
 namespace {
 
-constexpr size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // gb_kernel's carve (gb.hip, M | Y | X | cnt | flag): one plane word per slot and per variable,
 // the decision planes X only under early stop or Monte-Carlo, then one count per codeword of the
 // workgroup and the three syndrome flags.
 size_t gb_lds(int n, int E, bool has_x, int plane) {
     return pad16(((size_t)E + (has_x ? 2 : 1) * (size_t)n) * plane) + (size_t)4 * 8 * plane + 16;
 }
-
-// The shapes the ladder below can give, gb.hip's instantiations (launch_gb), by display name:
-// [early stop][Monte-Carlo]
-struct GbShape {
-    int T, plane;
-    const char *name[2][2];
-};
-constexpr GbShape kGbShapes[] = {
-    {256, 4, {{"gb_kernel<256,u32>", "gb_kernel<256,u32,mc>"}, {"gb_kernel<256,u32,es>", "gb_kernel<256,u32,es,mc>"}}},
-    {1024, 4, {{"gb_kernel<1024,u32>", "gb_kernel<1024,u32,mc>"}, {"gb_kernel<1024,u32,es>", "gb_kernel<1024,u32,es,mc>"}}},
-    {1024, 2, {{"gb_kernel<1024,u16>", "gb_kernel<1024,u16,mc>"}, {"gb_kernel<1024,u16,es>", "gb_kernel<1024,u16,es,mc>"}}},
-    {1024, 1, {{"gb_kernel<1024,u8>", "gb_kernel<1024,u8,mc>"}, {"gb_kernel<1024,u8,es>", "gb_kernel<1024,u8,es,mc>"}}},
-};
 
 }  // namespace
 
@@ -39,7 +24,13 @@ GbPlan gb_plan(int n, int E, int B, int iters, bool early_stop, bool mc) {
     for (int plane : {4, 2, 1}) {
         const size_t lds = gb_lds(n, E, has_x, plane);
         if (lds > kGbLdsCap) continue;
-        p.threads = plane == 4 && n <= 2048 ? 256 : 1024;
+        // the instantiation: the shape table's row (kernel_shapes.hpp, what gb.hip compiles).  Every
+        // (threads, plane) of this ladder has one; a shape without a row would be no plan.
+        const int T = plane == 4 && n <= 2048 ? 256 : 1024;
+        const auto *row = shapes::find(shapes::kGb, [&](const shapes::Gb &r) { return r.T == T && r.plane == plane; });
+        if (!row) break;
+        p.name = row->name[early_stop][mc];
+        p.threads = T;
         p.W = 1;
         p.plane = plane;
         p.cw_per_wg = 8 * plane;
@@ -47,8 +38,6 @@ GbPlan gb_plan(int n, int E, int B, int iters, bool early_stop, bool mc) {
         p.lds = lds;
         p.cap = kGbLdsCap;
         p.scratch = mc ? (size_t)4 * B * ((size_t)iters + 2) : 0;
-        for (const GbShape &s : kGbShapes)
-            if (s.T == p.threads && s.plane == plane) p.name = s.name[early_stop][mc];
         break;
     }
     return p;

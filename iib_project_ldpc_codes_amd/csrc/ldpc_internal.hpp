@@ -1,5 +1,7 @@
-// Internal declarations shared by the host files (capi.cpp, graph_host.cpp, graph_device.cpp, bp_plan.cpp, bec_plan.cpp, sample_plan.cpp) and the kernels
-// (bec.hip, bp_*.hip, mc_kernels.hip, ml.hip, sampler.hip, peel.hip).  Not part of the public ABI (see include/ldpc_mi355x.h).
+// Internal declarations shared by the host files (capi.cpp, mc_run.cpp, graph_host.cpp, graph_device.cpp, loc_layout.cpp,
+// encode_host.cpp and the launch plans bp_plan.cpp, bec_plan.cpp, gb_plan.cpp, encode_plan.cpp, sample_plan.cpp) and the
+// kernels (bec.hip, peel.hip, gb.hip, encode.hip, bp_*.hip, mc_kernels.hip, ml.hip, sampler.hip).  Not part of the public
+// ABI (see include/ldpc_mi355x.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +9,8 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+
+#include "kernel_shapes.hpp"
 
 struct ldpc_quant;  // include/ldpc_mi355x.h
 
@@ -131,19 +135,19 @@ inline void loc_shape(const LocLayout &K, GraphShape &g) {
 // WHOLE shape, never from the check degrees alone (a check-regular degree-6 graph with
 // variable degrees {2, 4} has loc_dlo == 6 but needs the RSU family's DVN = 3 rows):
 //   kLocReg36: <DLO=6, DHI=6, DVN0=2, DVN1=2, ABS0=ABS1=false> -- every check degree 6 and every
-//              variable degree 3 (the (3,6) codes); shapes T=256 KP 1-4, T=1024 KP 2-3, T=512 KP 5
+//              variable degree 3 (the (3,6) codes)
 //   kLocRsu:   <DLO=5, DHI=6, DVN0=1, DVN1=3, ABS0=false, ABS1=true> -- check degrees 5..6, every
-//              slot-0 variable degree 2, slot-1 variables degree 2..4; T=256 KP 1-4, T=1024 KP 2-3,
-//              T=512 KP 8 / 10
+//              slot-0 variable degree 2, slot-1 variables degree 2..4
 //   kLocNone:  no instantiation (the graph runs on bp_lds / bp_irr / bp_generic)
+// Each family has the (T, KP) rows of its shape table (kernel_shapes.hpp), which bp_loc.hpp instantiates.
 enum LocVariant { kLocNone = 0, kLocReg36 = 1, kLocRsu = 2 };
 inline int loc_variant(int dlo, int dhi, int DVN, int dvn0, int dvn1, bool abs0, bool abs1, int T, int KP) {
     if (KP <= 0) return kLocNone;
     const bool reg36 = dlo == 6 && dhi == 6 && DVN == 2 && dvn0 == 2 && dvn1 == 2 && !abs0 && !abs1;
     const bool rsu = !reg36 && dlo >= 5 && dhi == 6 && DVN == 3 && dvn0 == 1 && !abs0 && dvn1 <= 3;
-    const bool common = (T == 256 && KP >= 1 && KP <= 4) || (T == 1024 && KP >= 2 && KP <= 3);
-    if (reg36 && (common || (T == 512 && KP == 5))) return kLocReg36;
-    if (rsu && (common || (T == 512 && (KP == 8 || KP == 10)))) return kLocRsu;
+    const auto row = [&](const ldpc::shapes::Shape2 &r) { return r.T == T && r.per_thread == KP; };
+    if (reg36 && ldpc::shapes::find(ldpc::shapes::kLocReg36, row)) return kLocReg36;
+    if (rsu && ldpc::shapes::find(ldpc::shapes::kLocRsu, row)) return kLocRsu;
     return kLocNone;
 }
 inline int loc_variant(const GraphShape &g) {
@@ -159,23 +163,22 @@ constexpr size_t kIrrLdsMsgBytes = 148 * 1024;
 // for block length n: >= 2 % spare lanes for the conflict-aware layout.  (At
 // n = 10^4, 3 % spare = 11 variables per thread packs with ~1.02 LDS cycles per
 // half-wave access, 2 % = 10 per thread with ~1.5 -- and is 5 % faster: the
-// variable phase is bound by per-lane work, not bank conflicts.)  Must match the
-// instantiations in bp_lds.hip.
+// variable phase is bound by per-lane work, not bank conflicts.)  The first row of the shape
+// table (kernel_shapes.hpp, what bp_lds.hip instantiates) with enough lanes: the 256-thread rows
+// up to n = 2048, the 1024-thread rows beyond and where those do not reach.
 #ifndef LDPC_LDS_SPARE
 #define LDPC_LDS_SPARE 102  // lanes >= n * SPARE / 100 (fewer lanes beat fewer bank conflicts)
 #endif
 inline bool lds_shape(int n, int &T, int &VPT) {
-    static const int v256[] = {1, 2, 3, 5, 9};
-    static const int v1024[] = {2, 3, 5, 6, 9, 10, 11, 14};
     const long need = ((long)n * LDPC_LDS_SPARE + 99) / 100;
-    if (n <= 2048) {
-        T = 256;
-        for (int v : v256)
-            if (256L * v >= need) { VPT = v; return true; }
+    for (int t : {256, 1024}) {
+        if (t == 256 && n > 2048) continue;
+        T = t;
+        const auto *r = ldpc::shapes::find(ldpc::shapes::kLds36, [&](const ldpc::shapes::Shape2 &s) {
+            return s.T == t && (long)t * s.per_thread >= need;
+        });
+        if (r) { VPT = r->per_thread; return true; }
     }
-    T = 1024;
-    for (int v : v1024)
-        if (1024L * v >= need) { VPT = v; return true; }
     return false;
 }
 constexpr size_t kLdsMax = 160 * 1024;  // LDS bytes of one CU (the launch plans budget against it)
@@ -202,6 +205,7 @@ inline int lds_pair_span(int m, int dc) { return ((m + 1) / 2) * 2 * dc; }
 namespace ldpc {
 
 void set_error(const std::string &msg);
+constexpr size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }  // LDS carves keep 16-byte alignment
 
 // The launch plan of one BEC call (bec_plan.cpp): which kernel runs and everything its launch
 // needs, decided in one host-only function; bec.hip and peel.hip launch what it says.
@@ -306,18 +310,18 @@ BpPlan bp_layer_plan(const GraphShape &g, int B, int iters, int algo, bool early
 BpPlan bp_layer_q_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
                        int cus);
 constexpr size_t layer_q_record_bytes(int max_cdeg) { return max_cdeg <= 16 ? 4 : 8; }
-constexpr size_t layer_block_bytes(size_t n, size_t E) { return ((n + E) * 4 + 15) & ~(size_t)15; }
+constexpr size_t layer_block_bytes(size_t n, size_t E) { return pad16((n + E) * 4); }
 // Row l of lay_tab: [j] (j <= 32) = first word of the layer's j-th edges in lay_var (and in R): the
 // checks of a layer are sorted by falling degree, so position p of the layer has a j-th edge
 // exactly when p < [j + 1] - [j] (and [1] - [0] is the layer's number of checks); [32] is the
 // layer's end, the next row's [0].
 constexpr int kLayerMaxD = 32, kLayerTab = kLayerMaxD + 1;
-constexpr size_t ens_block_bytes(size_t n, size_t E) { return (E * 8 + n * 4 + 15) & ~(size_t)15; }
+constexpr size_t ens_block_bytes(size_t n, size_t E) { return pad16(E * 8 + n * 4); }
 // bp_generic_kernel's block: messages float[E] | channel LLRs float[n] | decision bytes u8[E]
-constexpr size_t generic_block_bytes(size_t n, size_t E) { return (E * 5 + n * 4 + 15) & ~(size_t)15; }
+constexpr size_t generic_block_bytes(size_t n, size_t E) { return pad16(E * 5 + n * 4); }
 // The Monte-Carlo curve (iters + 1 counts) where something follows it in LDS: 16-byte padded
-constexpr size_t curve_bytes(int iters) { return ((size_t)(iters + 1) * 4 + 15) & ~(size_t)15; }
-constexpr size_t ens_syn_bytes(size_t m) { return (2 * ((m + 31) / 32) * 4 + 15) & ~(size_t)15; }
+constexpr size_t curve_bytes(int iters) { return pad16((size_t)(iters + 1) * 4); }
+constexpr size_t ens_syn_bytes(size_t m) { return pad16(2 * ((m + 31) / 32) * 4); }
 // Compute units of the current device (256 when it cannot be queried), asked on every call:
 // devices launch from their own host threads, and the slabs and the grid must agree per device.
 int device_cus();

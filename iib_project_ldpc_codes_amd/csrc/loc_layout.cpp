@@ -229,7 +229,18 @@ bool build_loc_layout(int n, int m, const std::vector<int32_t> &cptr, const std:
         else L.ABS1 |= nd != L.DVN1;
     }
     L.KP = (L.P + L.T - 1) / L.T;
-    if (L.T == 512) L.KP = L.KP <= 5 ? 5 : (L.KP <= 8 ? 8 : 10);  // the instantiated 512-thread shapes
+    if (L.T == 512) {  // the instantiated 512-thread shapes: the smallest row of the shape table
+                       // (kernel_shapes.hpp, either variant) that holds the pairs, else the largest
+        int fit = 0, top = 0;
+        const auto row = [&](const ldpc::shapes::Shape2 &r) {
+            if (r.T != 512) return;
+            top = std::max(top, r.per_thread);
+            if (r.per_thread >= L.KP && (!fit || r.per_thread < fit)) fit = r.per_thread;
+        };
+        for (const auto &r : ldpc::shapes::kLocReg36) row(r);
+        for (const auto &r : ldpc::shapes::kLocRsu) row(r);
+        L.KP = fit ? fit : top;
+    }
     if ((long)L.KP * L.T < L.P || L.words + 64 >= 65536) return false;  // beyond 16-bit words / the shapes
     // Bank-conflict search.  A variable's non-local edge u is gathered (and written) by
     // one instruction (var pair slot, u, half) of its thread; the 32 lanes of a half wave

@@ -269,14 +269,10 @@ hipError_t launch_ml_decode(const int32_t *cptr, const int32_t *cvar, int64_t cv
     const int W = ml_words(m);
     const int T = std::min(1024, std::max(64, (m + 63) / 64 * 64));
     const size_t lds = ml_lds_bytes(n, m, W, T);
-#define LDPC_ML_CASE(WW)                                                                                    \
-    case WW: {                                                                                              \
-        hipError_t e = allow_lds(ml_kernel<WW>, lds);                                                       \
-        if (e != hipSuccess) return e;                                                                      \
-        hipLaunchKernelGGL(ml_kernel<WW>, dim3(B), dim3(T), lds, stream, cptr, cvar, cvar_stride, dc, n, m, \
-                           d_in, d_out, d_unsolved);                                                        \
-        return hipGetLastError();                                                                           \
-    }
+#define LDPC_ML_CASE(WW)                                                                                        \
+    case WW:                                                                                                    \
+        return launch_lds(ml_kernel<WW>, dim3(B), dim3(T), lds, stream, cptr, cvar, cvar_stride, dc, n, m, d_in, \
+                          d_out, d_unsolved);
     switch (W) {
         LDPC_ML_CASE(1)
         LDPC_ML_CASE(2)

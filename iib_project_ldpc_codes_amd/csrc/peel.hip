@@ -175,10 +175,7 @@ hipError_t launch_mc_bec_peel(const BecPlan &plan, int n, int m, int dv, int dc,
     a.first_cw = first_cw;
     a.trial = trial;
     a.its = trial_its;
-    hipError_t e = allow_lds(bec_peel_kernel<1024>, plan.lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bec_peel_kernel<1024>, dim3((unsigned)plan.grid), dim3(plan.threads), plan.lds, stream, a);
-    return hipGetLastError();
+    return launch_lds(bec_peel_kernel<1024>, dim3((unsigned)plan.grid), dim3(plan.threads), plan.lds, stream, a);
 }
 
 hipError_t peel_stats(uint64_t *out, int reset) {

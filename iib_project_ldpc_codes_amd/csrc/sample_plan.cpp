@@ -16,10 +16,15 @@ constexpr size_t kVarSideLds = 150 * 1024;  // the variable-side kernel's rows a
 void one_level(SamplePlan &p, int n, int E) {
     const int K = sample_buckets(E);
     const bool lds = n <= 65536 && K < 1024;
-    p.threads = p.K = lds ? K : 1024;
+    // the instantiation: the shape table's row (kernel_shapes.hpp, what sampler.hip compiles).  Every
+    // (buckets, lds) these rules give has one; a shape without a row would be no plan (threads = 0).
+    const auto *row = shapes::find(shapes::kSampleLevel, [&](const shapes::SampleLevel &r) {
+        return r.K == (lds ? K : 1024) && r.lds == lds;
+    });
+    if (!row) return;
+    p.threads = p.K = row->K;
     p.lds = (size_t)4 * (p.K * (p.K / kWaveLanes) + 16) + (lds ? (size_t)2 * E : 0);
-    p.draw = !lds ? "sample_regular_kernel<1024,int32,gmem>"
-                  : (K == 256 ? "sample_regular_kernel<256,u16,lds>" : "sample_regular_kernel<512,u16,lds>");
+    p.draw = row->name;
 }
 
 }  // namespace
@@ -37,20 +42,23 @@ SamplePlan sample_plan(int n, int m, int E, int max_cdeg, int max_vdeg, bool reg
     p.bw = ((E + 31) / 32 + 3) & ~3;
     p.fb = max_vdeg <= 3 ? 2 : (max_vdeg <= 15 ? 4 : (max_vdeg <= 255 ? 8 : 0));
     p.fbu = p.fb && (long)n * p.fb <= (long)p.bw * 32 ? p.fb : 0;
-    const bool r16 = n <= 65536;  // variable ids fit the u16 ring
-    p.ring = r16 ? 2 : 4;
+    p.ring = n <= 65536 ? 2 : 4;  // variable ids fit the u16 ring
+    // the draw and search kernels' instantiation: the row of (csr, ring), as the launcher reads them.
+    // Both choices have all four rows; a pair without one would be no plan (threads = 0).
+    const auto *form = shapes::find(shapes::kSampleSeq, [&](const shapes::SampleSeq &r) {
+        return r.csr == p.csr && r.ring == p.ring;
+    });
+    if (!form) return p;
     p.threads = kSeqThreads;
     p.lds = seq_plan_lds(p.bw, p.ring);
-    p.draw = regular ? (r16 ? "sample_seq_kernel<regular,u16>" : "sample_seq_kernel<regular,int>")
-                     : (r16 ? "sample_seq_kernel<csr,u16>" : "sample_seq_kernel<csr,int>");
+    p.draw = form->seq;
     p.mdv = regular && dv > 1 && dv < 256 ? (uint32_t)((0x100000000ull + dv - 1) / dv) : 0u;
     if (cus > 0 && G > 0) {
         // search pass: persistent workgroups, as many as fit the device (LDS bound), at most one
         // pool row each in the G rows of variable_lookup
         p.per_cu = (int)std::max<long>(1, std::min<long>(32, (long)kLdsMax / (long)p.lds));
         p.W = (int)std::min<long>((long)G, (long)cus * p.per_cu);
-        p.search = regular ? (r16 ? "sample_search_kernel<regular,u16>" : "sample_search_kernel<regular,int>")
-                           : (r16 ? "sample_search_kernel<csr,u16>" : "sample_search_kernel<csr,int>");
+        p.search = form->search;
     }
     // variable side: chunks of V variables per workgroup after the emit pass, rows of at most
     // max_vdeg entries staged in LDS (u16 entries when every check / slot id fits) within 150 KiB
@@ -61,12 +69,16 @@ SamplePlan sample_plan(int n, int m, int E, int max_cdeg, int max_vdeg, bool reg
         p.V = (int)std::min<size_t>((size_t)n, kVarSideLds * 8 / bits) & ~63;
         if (p.V < 64) p.V = 0;
     }
+    // the variable-side kernel's instantiation: the row of `row` (both widths have one; without
+    // it there would be no such kernel, and the emit pass would do its work)
+    const auto *vs = shapes::find(shapes::kSampleVarSide, [&](const shapes::SampleVarSide &r) { return r.row == p.row; });
+    if (!vs) p.V = 0;
     p.emit_fb = p.V ? -1 : p.fbu;
     if (!p.V) return p;
     p.nch = (n + p.V - 1) / p.V;
     // counters (words, rounded up to 4) | rows
     p.vs_lds = (size_t)4 * ((((size_t)p.V * p.fb + 31) / 32 + 3) / 4 * 4) + (size_t)p.row * p.V * max_vdeg;
-    p.var_side = u16rows ? "sample_var_side_kernel<1024,u16>" : "sample_var_side_kernel<1024,int32>";
+    p.var_side = vs->name;
     return p;
 }
 

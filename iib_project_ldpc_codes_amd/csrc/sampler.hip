@@ -1073,6 +1073,42 @@ __global__ __launch_bounds__(T) void sample_regular_kernel(SampleShape sh, uint3
     sample_emit_var_side(sh, chk, vl);
 }
 
+// Every launch below runs the row of its shape table (kernel_shapes.hpp) that sample_plan selected,
+// found by the plan's own fields; no row: hipErrorInvalidValue (the plan gives none).  The helpers
+// stand in the order of the kernels in the code object: one level, sequential draw, search.
+
+// One Rao-Sandelius level on the plan's K buckets
+hipError_t launch_level(const SamplePlan &p, const SampleShape &sh, uint32_t k0, uint32_t k1, uint64_t first_graph, int G,
+                        int32_t *check_lookup, int32_t *variable_lookup, int32_t *attempts, int max_attempts,
+                        hipStream_t stream) {
+#define LDPC_ROW(KK, IDX, TAG, LDSBUF, MEM)                                                                      \
+    if (p.K == KK)                                                                                               \
+        return launch_lds(sample_regular_kernel<KK, IDX, LDSBUF>, dim3(G), dim3(KK), p.lds, stream, sh, k0, k1, \
+                          first_graph, check_lookup, variable_lookup, attempts, max_attempts);
+    LDPC_SAMPLE_LEVEL_SHAPES(LDPC_ROW)
+#undef LDPC_ROW
+    return hipErrorInvalidValue;
+}
+
+// The sequential sampler's kernels for the plan's (csr, ring): those of the shape table's row
+// (kernel_shapes.hpp) from which sample_plan took their names; nullptr where the plan has none.
+struct SeqKernels {
+    decltype(&sample_seq_kernel<false, int>) draw;
+    decltype(&sample_search_kernel<false, int>) search;
+};
+SeqKernels seq_kernels(const SamplePlan &p) {
+    SeqKernels k{nullptr, nullptr};
+    // two passes over the rows: every draw kernel is named before the first search kernel, which
+    // is their order in the code object
+#define LDPC_ROW(CSR, FORM, IDX, TAG) if (p.csr == CSR && p.ring == (int)sizeof(IDX)) k.draw = sample_seq_kernel<CSR, IDX>;
+    LDPC_SAMPLE_SEQ_SHAPES(LDPC_ROW)
+#undef LDPC_ROW
+#define LDPC_ROW(CSR, FORM, IDX, TAG) if (p.csr == CSR && p.ring == (int)sizeof(IDX)) k.search = sample_search_kernel<CSR, IDX>;
+    LDPC_SAMPLE_SEQ_SHAPES(LDPC_ROW)
+#undef LDPC_ROW
+    return k;
+}
+
 }  // namespace
 
 // Launches what sample_plan (sample_plan.cpp) says: the draw kernel (after the search pass when
@@ -1082,63 +1118,48 @@ static hipError_t launch_sample(const SampleShape &sh, int max_cdeg, int max_vde
                                 int32_t *attempts, int max_attempts, uint32_t *ctl, hipStream_t stream) {
     if (G <= 0) return hipSuccess;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const bool csr = sh.vsock != nullptr;
+    const bool regular = sh.vsock == nullptr;
     // the plan without a device first; the device is asked for its CUs only where a search pass
     // can run (a sequential plan and `ctl` given), and the plan made again with them
-    SamplePlan p = sample_plan(sh.n, sh.m, sh.E, max_cdeg, max_vdeg, !csr, sh.dv, G, 0);
+    SamplePlan p = sample_plan(sh.n, sh.m, sh.E, max_cdeg, max_vdeg, regular, sh.dv, G, 0);
     hipError_t e = hipSuccess;
     if (p.seq && ctl) {
         int dev = 0, cus = 0;
         e = hipGetDevice(&dev);
         if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         if (e != hipSuccess) return e;
-        p = sample_plan(sh.n, sh.m, sh.E, max_cdeg, max_vdeg, !csr, sh.dv, G, cus);
+        p = sample_plan(sh.n, sh.m, sh.E, max_cdeg, max_vdeg, regular, sh.dv, G, cus);
     }
-#define LDPC_SAMPLE(TT, IDX, LDSB)                                                                             \
-    do {                                                                                                       \
-        auto k = sample_regular_kernel<TT, IDX, LDSB>;                                                         \
-        if ((e = allow_lds(k, p.lds)) != hipSuccess) return e;                                                 \
-        hipLaunchKernelGGL(k, dim3(G), dim3(TT), p.lds, stream, sh, k0, k1, first_graph, check_lookup,         \
-                           variable_lookup, attempts, max_attempts);                                           \
-        return hipGetLastError();                                                                              \
-    } while (0)
-    if (!p.seq) {
-        if (p.K == 256) LDPC_SAMPLE(256, uint16_t, true);
-        if (p.K == 512) LDPC_SAMPLE(512, uint16_t, true);
-        LDPC_SAMPLE(1024, int32_t, false);
-    }
-#undef LDPC_SAMPLE
-    const bool r16 = p.ring == 2;
-    auto kern = csr ? (r16 ? sample_seq_kernel<true, uint16_t> : sample_seq_kernel<true, int>)
-                    : (r16 ? sample_seq_kernel<false, uint16_t> : sample_seq_kernel<false, int>);
-    if ((e = allow_lds(kern, p.lds)) != hipSuccess) return e;
+    if (!p.seq)
+        return launch_level(p, sh, k0, k1, first_graph, G, check_lookup, variable_lookup, attempts, max_attempts, stream);
+    const SeqKernels k = seq_kernels(p);
+    if (!k.draw) return hipErrorInvalidValue;
     const uint32_t *start = nullptr, *homewin = nullptr;
     if (p.W) {
         // search pass: p.W persistent workgroups, at most one pool row each in the 2G rows of the
         // two outputs
-        auto sk = csr ? (r16 ? sample_search_kernel<true, uint16_t> : sample_search_kernel<true, int>)
-                      : (r16 ? sample_search_kernel<false, uint16_t> : sample_search_kernel<false, int>);
-        if ((e = allow_lds(sk, p.lds)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(ctl, 0, 8, stream)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(ctl + 2, 0xFF, (size_t)4 * G, stream)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(ctl + 2 + G, 0, (size_t)4 * G, stream)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(ctl + 2 + 2 * G, 0xFF, (size_t)4 * G, stream)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(ctl + 2 + 3 * G, 0, (size_t)4 * G, stream)) != hipSuccess) return e;
         // graphs' home waves draw into check_lookup; pool rows: wave w uses variable_lookup row w
-        hipLaunchKernelGGL(sk, dim3(p.W), dim3(kSeqT), p.lds, stream, sh, k0, k1, first_graph, G, check_lookup,
-                           variable_lookup, ctl, max_attempts, p.bw, p.mdv);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        e = launch_lds(k.search, dim3(p.W), dim3(kSeqT), p.lds, stream, sh, k0, k1, first_graph, G, check_lookup,
+                       variable_lookup, ctl, max_attempts, p.bw, p.mdv);
+        if (e != hipSuccess) return e;
         start = ctl + 2;
         homewin = ctl + 2 + 2 * G;
     }
-    hipLaunchKernelGGL(kern, dim3(G), dim3(kSeqT), p.lds, stream, sh, k0, k1, first_graph, check_lookup,
-                       variable_lookup, attempts, max_attempts, p.bw, p.emit_fb, p.mdv, start, homewin);
-    if ((e = hipGetLastError()) != hipSuccess || !p.V) return e;
-    auto vk = p.row == 2 ? sample_var_side_kernel<1024, uint16_t> : sample_var_side_kernel<1024, int32_t>;
-    if ((e = allow_lds(vk, p.vs_lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(vk, dim3((unsigned)G * p.nch), dim3(1024), p.vs_lds, stream, sh, check_lookup, variable_lookup,
-                       G, p.V, p.fb, max_vdeg);
-    return hipGetLastError();
+    e = launch_lds(k.draw, dim3(G), dim3(kSeqT), p.lds, stream, sh, k0, k1, first_graph, check_lookup, variable_lookup,
+                   attempts, max_attempts, p.bw, p.emit_fb, p.mdv, start, homewin);
+    if (e != hipSuccess || !p.V) return e;
+#define LDPC_ROW(T, IDX, TAG)                                                                                      \
+    if (p.row == (int)sizeof(IDX))                                                                                 \
+        return launch_lds(sample_var_side_kernel<T, IDX>, dim3((unsigned)G * p.nch), dim3(T), p.vs_lds, stream, sh, \
+                          check_lookup, variable_lookup, G, p.V, p.fb, max_vdeg);
+    LDPC_SAMPLE_VAR_SIDE_SHAPES(LDPC_ROW)
+#undef LDPC_ROW
+    return hipErrorInvalidValue;
 }
 
 hipError_t seq_stats(uint64_t *out, int reset) {

@@ -18,6 +18,9 @@ from tests import graph_util
 
 NAMES = ("r36_12", "r36_96", "r36_1000", "r48_64", "mixA", "mixB", "twice", "lonely", "square")
 GPU_NAMES = tuple(n for n in NAMES if n != "mixA")  # n <= 1,000
+# wide_<K>: the smallest K whose information planes leave the tile of 4 plane words, and of 2 (4 K W bytes
+# past 160 - 4 KiB): the encoder's tiles of 2 and of 1
+TILE_NAMES = (("wide_9985", 2), ("wide_19969", 1))
 
 
 @functools.lru_cache(maxsize=None)
@@ -40,6 +43,12 @@ def graph(name):
     elif name == "lonely":
         cptr, cvar, _ = graph("r36_96")
         return _frozen(cptr, cvar, 97)
+    elif name.startswith("wide_"):
+        # 16 disjoint checks over K + 16 variables (variable v in check v mod 16): rank 16, K information bits
+        n = int(name.split("_")[1]) + 16
+        cvar = np.concatenate([np.arange(c, n, 16) for c in range(16)])
+        cptr = np.concatenate([[0], np.cumsum([len(range(c, n, 16)) for c in range(16)])])
+        return _frozen(cptr, cvar, n)
     elif name == "square":
         cvar = np.concatenate([[0]] + [[c, c - 1] for c in range(1, 40)])
         cptr = np.concatenate([[0, 1], 1 + 2 * np.arange(1, 40)])

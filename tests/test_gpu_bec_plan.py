@@ -2,9 +2,11 @@
 reaches it: each case first holds the call to the kernel its plan names (ldpc_debug_bec_plan,
 tests/test_bec_plan.py holds the plan itself), then compares bit for bit with the oracle's
 message_passing.c restatement.  (3,6) random_regular graphs, eps = 0.42, 20 iterations unless
-said.  Without a GPU run, as before: bec_dec_bits_kernel<512,4,u32> (no rate-1/2 graph plans to
-it) and bec_mc_bits_kernel<512,2|4,u32>.
+said.  bec_dec_bits_kernel<512,4,u32> (no rate-1/2 graph plans to it) and
+bec_mc_bits_kernel<512,2|4,u32> run on a graph of few checks (test_decode_wide_512, test_mc_wide_512).
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -83,6 +85,70 @@ def test_mc(torch, n, B, iters, name):
     words = oracle.channel(oracle.CH_BEC, EPS, 9, 0, n, B)
     _, err, its = oracle.bec_decode_batch(words, iters, g.variable_lookup, g.check_lookup, n, n // 2, 3, 6)
     curves = np.concatenate([np.count_nonzero(words == 2, axis=1)[:, None], err], axis=1)
+    want = np.concatenate([[B, np.count_nonzero(curves[:, -1]), curves[:, -1].sum(), its.sum()], curves.sum(axis=0)])
+    np.testing.assert_array_equal(got, want)
+
+
+# The 512-thread rows that no rate-1/2 graph reaches need n > 4,096 with n + m small enough for four
+# plane words within 72 KiB: 4,112 variables of degree 1 in 257 checks of degree 16 (the first multiple
+# of 16 past 4,096).  Wider plane words are taken only from 1,024 workgroups on, so each case runs at
+# the smallest B that selects its row (one codeword past 1,023 workgroups), not at one plane word plus
+# one, and asserts that one codeword fewer selects the narrower row.
+WIDE_N, WIDE_DC, WIDE_ITERS, WIDE_EPS = 4112, 16, 3, 0.1
+WIDE_MC = [(65473, "bec_mc_bits_kernel<512,2,u32>", "bec_mc_bits_kernel<512,1,u32>"),
+           (130945, "bec_mc_bits_kernel<512,4,u32>", "bec_mc_bits_kernel<512,2,u32>")]
+
+
+def _wide_graph():
+    from iib_project_ldpc_codes_amd.graph import TannerGraph
+    if "wide" not in _graphs:
+        _graphs["wide"] = TannerGraph.random_regular(WIDE_N, 1, WIDE_DC, seed=11)
+    return _graphs["wide"]
+
+
+def _wide_name(mode, B):
+    return bec_plans(WIDE_N, WIDE_N // WIDE_DC, [(mode, B, WIDE_ITERS)], dc=WIDE_DC)[0]["name"]
+
+
+def test_decode_wide_512(torch):
+    """bec_dec_bits_kernel<512,4,u32>: as test_decode, 65,473 words of 64 distinct ones."""
+    from iib_project_ldpc_codes_amd import decoder
+    n, B, iters = WIDE_N, 65473, WIDE_ITERS
+    assert _wide_name(BEC_DECODE, B) == "bec_dec_bits_kernel<512,4,u32>"
+    assert _wide_name(BEC_DECODE, B - 1) == "bec_dec_bits_kernel<512,2,u32>"
+    g = _wide_graph()
+    words, errin = _perturbed_bec_batch(n, DISTINCT, WIDE_EPS, iters, seed=n + B)
+    ow, oerr, oits = oracle.bec_decode_batch(words, iters, g.variable_lookup, g.check_lookup, n, g.k, 1, WIDE_DC,
+                                             errors=errin)
+    assert 0 < np.count_nonzero(ow == 2) < np.count_nonzero(words == 2)  # some erasures decode, some stay
+    row = np.arange(B) % len(words)
+    w, err, its = decoder.bec_decode(g, words[row], iters, errors=errin[row])
+    np.testing.assert_array_equal(w.astype(np.int8), ow[row])
+    np.testing.assert_array_equal(err, oerr[row])
+    np.testing.assert_array_equal(its, oits[row])
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_mc_reference():
+    """Per-trial error curves and iteration counts of trials 0 .. 130,944 (the oracle's channel and
+    decoder, once for both cases: trial b does not depend on the batch it is drawn in)."""
+    g, B = _wide_graph(), max(b for b, _, _ in WIDE_MC)
+    words = oracle.channel(oracle.CH_BEC, WIDE_EPS, 9, 0, WIDE_N, B)
+    erased = np.count_nonzero(words == 2, axis=1)
+    _, err, its = oracle.bec_decode_batch(words, WIDE_ITERS, g.variable_lookup, g.check_lookup, WIDE_N, g.k, 1, WIDE_DC)
+    curves = np.concatenate([erased[:, None], err], axis=1)
+    for a in (curves, its):
+        a.setflags(write=False)
+    return curves, its
+
+
+@pytest.mark.parametrize("B,name,narrower", WIDE_MC)
+def test_mc_wide_512(torch, B, name, narrower):
+    """bec_mc_bits_kernel<512,2,u32> and <512,4,u32>: every counter and the curve, as test_mc."""
+    assert _wide_name(BEC_MC, B) == name and _wide_name(BEC_MC, B - 1) == narrower
+    got = _mc_counters(_wide_graph(), "bec", WIDE_EPS, 9, B, WIDE_ITERS)
+    curves, its = (a[:B] for a in _wide_mc_reference())
+    assert 0 < curves[:, -1].sum() < curves[:, 0].sum()  # some erasures decode, some stay
     want = np.concatenate([[B, np.count_nonzero(curves[:, -1]), curves[:, -1].sum(), its.sum()], curves.sum(axis=0)])
     np.testing.assert_array_equal(got, want)
 

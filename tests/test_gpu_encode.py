@@ -65,6 +65,25 @@ def test_encode_against_reference(torch, name):
         assert not enc.encode(np.zeros((33, 0), np.uint8)).any()
 
 
+@pytest.mark.parametrize("name,W", eu.TILE_NAMES)
+def test_encode_narrower_tiles(torch, name, W):
+    """encode_parity_kernel<2> and <1> (every graph above runs <4>) at the smallest K that selects each,
+    33 codewords (a whole plane word and one more): the plan first, then the reference bit for bit."""
+    from iib_project_ldpc_codes_amd.encoder import Encoder
+    H = eu.H(name)
+    n = H.shape[1]
+    enc = Encoder(eu.tanner(name))
+    rank, info, par, _ = eu.description(name)
+    assert (enc.rank, enc.K) == (rank, n - rank) == (16, n - 16)
+    rc, rows = eu.encode_plans([(n, enc.K, rank, 33), (n - 1, enc.K - 1, rank, 33)])
+    assert rc == 0 and [r["name"] for r in rows] == ["encode_parity_kernel<%d>" % W, "encode_parity_kernel<%d>" % (2 * W)]
+    U = np.random.default_rng(3).integers(0, 2, (33, enc.K)).astype(np.uint8)
+    want = encode_ref.solve(H, info, par, U)
+    x = enc.encode(U)
+    np.testing.assert_array_equal(x, want)
+    assert not (H.astype(np.int64) @ x.T.astype(np.int64) & 1).any()
+
+
 def test_encode_unaligned_output(torch):
     """An output that starts at an odd byte: the byte-store form (as for `lonely`, n = 97)."""
     from iib_project_ldpc_codes_amd.encoder import Encoder

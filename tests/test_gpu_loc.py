@@ -76,6 +76,88 @@ def test_loc_minsum_bit_exact(torch, monkeypatch, kind, n):
     np.testing.assert_array_equal(hard, ohard)
 
 
+def _plan(csr, algo, env=None):
+    """Kernel name and threads of a 2-word, 5-iteration decode with posteriors (host-only plan)."""
+    from tests.graph_util import bp_plans
+    p = bp_plans(csr, [(algo, 0, 0, 1, 5, 2)], env=env)[0]
+    return p["name"], p["threads"]
+
+
+# Every row of the bp_lds_kernel<3,6> shape table (csrc/kernel_shapes.hpp) that a graph can reach (no n
+# reaches 1024 x 2), each at the smallest even n whose lane layout has that (threads, variables per
+# thread): just above threads x the row before / 1.02 (256 x 1: n = 96).
+LDS36_ROWS = [(96, 256, 1), (252, 256, 2), (502, 256, 3), (754, 256, 5), (1256, 256, 9), (2050, 1024, 3),
+              (3012, 1024, 5), (5020, 1024, 6), (6024, 1024, 9), (9036, 1024, 10), (10040, 1024, 11), (11044, 1024, 14)]
+
+
+@pytest.mark.parametrize("n,T,VPT", LDS36_ROWS)
+def test_lds36_every_shape(torch, monkeypatch, n, T, VPT):
+    """Min-sum on bp_lds_kernel<3,6> (the local-edge layout disabled), two words, five iterations:
+    bit-exact against the oracle at every (threads, variables per thread) of the table."""
+    from iib_project_ldpc_codes_amd import decoder
+    from tests.test_host_layouts import lane_layout
+    g, csr = _graph("reg", n, 21, True, monkeypatch)
+    lane = lane_layout((np.ascontiguousarray(g.variable_lookup, np.int32), np.ascontiguousarray(g.check_lookup, np.int32),
+                        n, n // 2, 3, 6))
+    assert (lane["T"], lane["VPT"]) == (T, VPT)
+    assert _plan(csr, 1, {"LDPC_NO_LOC_LAYOUT": "1"}) == ("bp_lds_kernel<3,6>", T)
+    assert g.kernel_name() == "bp_lds_kernel<3,6>"
+    llr = oracle.channel(oracle.CH_AWGN, 0.80, 6, 0, n, 2)
+    post, hard, its = decoder.bp_decode(g, llr, 5, "minsum", alpha=0.75)
+    opost, ohard, _ = oracle.bp_decode_batch(csr, llr, 5, 1, alpha=0.75)
+    np.testing.assert_array_equal(post, opost)
+    np.testing.assert_array_equal(hard, ohard)
+
+
+# The (3,6) rows of the bp_loc_kernel shape table that no other test launches, at the smallest n of
+# whole check pairs with that (threads, check pairs per thread): n / 4 = 256 (pairs - 1) + 1 pairs on
+# 256 threads, and 2,561 pairs, the first past the 512 x 5 shape, on 1,024.  (256 x 1 and 512 x 5 run
+# at n = 1,000 and 10,000 above; a (3,6) code never gets 1024 x 2: up to 2,560 pairs it takes 512
+# threads.)
+LOC36_ROWS = [(1028, 256, 2), (2052, 256, 3), (3076, 256, 4), (10244, 1024, 3)]
+
+
+@pytest.mark.parametrize("n,T,KP", LOC36_ROWS)
+def test_loc_reg36_every_shape(torch, monkeypatch, n, T, KP):
+    """Sum-product on bp_loc_kernel (min-sum runs on bp_lds_kernel<3,6> at these shapes), two words,
+    1, 3 and 5 iterations: posteriors within SPA_* of the oracle, as test_loc_spa_vs_oracle."""
+    from iib_project_ldpc_codes_amd import decoder
+    from tests.test_host_layouts import loc_layout, loc_variant
+    g, csr = _graph("reg", n, 21, False, monkeypatch)
+    assert _plan(csr, 0) == ("bp_loc_kernel", T)
+    assert loc_layout(csr, T)["shape"][:2] == [T, KP] and loc_variant(csr, T)["variant"] == 1
+    assert g.kernel_name() == "bp_loc_kernel"
+    llr = oracle.channel(oracle.CH_AWGN, 0.82, 5, 0, n, 2)
+    for iters in (1, 3, 5):
+        post, hard, its = decoder.bp_decode(g, llr, iters, "spa")
+        opost, ohard, _ = oracle.bp_decode_batch(csr, llr, iters, 0)
+        np.testing.assert_allclose(post, opost, rtol=SPA_RTOL, atol=SPA_ATOL)
+        assert np.all(its == iters)
+
+
+# The RSU-variant rows of the table that no case above launches (256 x 2 and 512 x 10 run at n = 2,000
+# and 20,000), at the smallest n of whole check pairs with that shape: 256 threads up to 1,024 pairs
+# (n / 4 = 256 (pairs - 1) + 1; 256 x 1: n = 500), 1,024 up to 3,072, 512 beyond.
+LOC_RSU_ROWS = [(500, 256, 1), (2052, 256, 3), (3076, 256, 4), (4100, 1024, 2), (8196, 1024, 3), (12292, 512, 8)]
+
+
+@pytest.mark.parametrize("n,T,KP", LOC_RSU_ROWS)
+def test_loc_rsu_every_shape(torch, monkeypatch, n, T, KP):
+    """Min-sum on bp_loc_kernel's RSU instantiation, two words, five iterations: bit-exact against
+    the oracle, as test_loc_minsum_bit_exact."""
+    from iib_project_ldpc_codes_amd import decoder
+    from tests.test_host_layouts import loc_layout, loc_variant
+    g, csr = _graph("rsu", n, 21, False, monkeypatch)
+    assert _plan(csr, 1) == ("bp_loc_kernel", T)
+    assert loc_layout(csr, T)["shape"][:2] == [T, KP] and loc_variant(csr, T)["variant"] == 2
+    assert g.kernel_name() == "bp_loc_kernel"
+    llr = oracle.channel(oracle.CH_AWGN, 0.80, 6, 0, g.n, 2)
+    post, hard, its = decoder.bp_decode(g, llr, 5, "minsum", alpha=0.75)
+    opost, ohard, _ = oracle.bp_decode_batch(csr, llr, 5, 1, alpha=0.75)
+    np.testing.assert_array_equal(post, opost)
+    np.testing.assert_array_equal(hard, ohard)
+
+
 @pytest.mark.parametrize("kind,n", [("reg", 10000), ("rsu", 20000)])
 def test_loc_spa_50_iterations(torch, monkeypatch, kind, n):
     """50 iterations: identical hard decisions on >= 99 % of frames and posteriors of those
