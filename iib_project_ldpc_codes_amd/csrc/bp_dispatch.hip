@@ -1,6 +1,6 @@
 // Soft decoding on a fixed code: the families' launches (ldpc_internal.hpp).  The caller's one
 // plan per call says which kernel and its launch shape; the kernel families' own files
-// (bp_lds.hip, bp_loc_*.hip, bp_irr.hip, bp_generic.hip, bp_layer.hip, bp_layer_q.hip) launch from it.
+// (bp_lds.hip, bp_loc_*.hip, bp_irr.hip, bp_generic.hip, bp_layer.hip, bp_layer_q.hip, bp_qc_q.hip) launch from it.
 #include "kernel_args.hpp"
 #include "ldpc_mi355x.h"
 
@@ -67,6 +67,11 @@ hipError_t LayerQFamily::launch(const BpPlan &p, const SoftCall &c, float *, hip
     a.Pmax = (1 << (q.post_bits - 1)) - 1;
     a.norm8 = q.norm8;
     a.offset = q.offset;
+    if (p.path >= BpPath::QcQ64x8) {  // a quasi-cyclic graph on its row table
+        if (!g.qc_row || g.qc_Z <= 0 || g.lay_L != g.qc_mb) return hipErrorNotSupported;
+        a.L = g.qc_mb;
+        return launch_qc_q(p, QcQArgs{a, g.qc_row, g.qc_Z}, c.early_stop, c.mc, s);
+    }
     return launch_layer_q(p, a, c.early_stop, c.mc, s);
 }
 

@@ -5,35 +5,20 @@
 //
 // One workgroup decodes one codeword at a time on a block
 //   posteriors P int8[n] (padded to 4 bytes) | one record per check, in layer order
-// in LDS.  The record holds what the check's messages R are rebuilt from: the two magnitudes
-// f(m1) and f(m2), the index i1 of the first minimum and one sign bit per edge --
-//   check degree <= 16: one word   f(m1) | f(m2) << 6 | i1 << 12 | signs << 16
-//   check degree <= 32: two words  f(m1) | f(m2) << 6 | i1 << 12,  signs
-// (magnitudes <= Q <= 63).  Record lay_cbase[l] + p belongs to the check at position p of layer l,
+// in LDS (the record's format, the quantiser and the step of one check: bp_layer_q.hpp, shared with
+// bp_qc_q.hip).  Record lay_cbase[l] + p belongs to the check at position p of layer l,
 // so the threads of a wave read neighbouring records.  As in bp_layer.hip thread i takes positions
 // i, i + T, ... of a layer and one workgroup barrier ends the layer; the checks of a layer share no
 // variable, so the byte stores to P of different threads never touch the same byte.
-#include "bp_device.hpp"
+#include "bp_layer_q.hpp"
 
 namespace ldpc {
 namespace {
 
-typedef __attribute__((address_space(3))) signed char lds_i8;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-
-// The channel quantiser: rint_half_even(clamp(l * scale, -Q, +Q)), NaN -> 0 (one fp32 product;
-// the library is built without contraction)
-__device__ __forceinline__ int quantise(float l, float scale, int Q) {
-    const float t = l * scale;
-    if (t != t) return 0;
-    return (int)__builtin_rintf(fminf(fmaxf(t, (float)-Q), (float)Q));
-}
-
 template <int T, int MAXDC, bool ET, bool MC>
 __global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int RW = MAXDC <= 16 ? 1 : 2;            // words of a record
-    constexpr uint32_t IMASK = MAXDC <= 16 ? 15 : 31;  // the index field
+    constexpr int RW = MAXDC <= 16 ? 1 : 2;  // words of a record
     const int tid = threadIdx.x;
     const int n = a.n, m = a.m, iters = a.max_iters, L = a.L;
     const int Q = a.Q, Pmax = a.Pmax, norm8 = a.norm8, offset = a.offset;
@@ -51,7 +36,6 @@ __global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a) {
             if ((tid & (kWave - 1)) == 0) atomicAdd(&curve[i], w);
         }
     };
-    auto f = [&](int mag) { return max(((mag * norm8) >> 3) - offset, 0); };
 
     // Variables and degree of the check at position p of a layer (bp_layer.hip's load_vars)
     auto load_vars = [&](const int32_t *row, int p, int &d, int (&v)[MAXDC]) {
@@ -63,55 +47,8 @@ __global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a) {
             d += has;
         }
     };
-    // The check with record c, degree d > 0 and variables v: every load before the first use
-    auto step = [&](int c, int d, const int (&v)[MAXDC]) {
-        int x[MAXDC];
-#pragma unroll
-        for (int j = 0; j < MAXDC; ++j) x[j] = P[v[j]];  // an absent edge reads byte 0
-        const uint32_t w0 = rec[c * RW];
-        const uint32_t sg = RW == 2 ? rec[c * RW + 1] : w0 >> 16;
-        const int f1 = w0 & 63, f2 = (w0 >> 6) & 63, i1 = (w0 >> 12) & IMASK;
-        // x_j = P - R_j, R_j rebuilt from the record; the min1 / min2 / index scan (an absent
-        // edge enters as magnitude Q, positive: it lowers neither minimum and is never first)
-        int a_[MAXDC];
-        uint32_t neg = 0;
-#pragma unroll
-        for (int j = 0; j < MAXDC; ++j) {
-            const int mag = j == i1 ? f2 : f1;
-            x[j] -= (sg >> j) & 1 ? -mag : mag;
-            const bool has = j < d;
-            a_[j] = has ? min(abs(x[j]), Q) : Q;
-            neg |= (uint32_t)(has && x[j] < 0) << j;
-        }
-        int m1 = a_[0], m2 = Q, k1 = 0;
-#pragma unroll
-        for (int j = 1; j < MAXDC; ++j) {
-            const bool lt = a_[j] < m1;
-            m2 = lt ? m1 : min(m2, a_[j]);
-            k1 = lt ? j : k1;
-            m1 = lt ? a_[j] : m1;
-        }
-        const int g1 = f(m1), g2 = f(m2);
-        const uint32_t par = __builtin_popcount(neg) & 1;
-        // r_j is negative iff parity ^ s_j, and |r_j| > 0
-        uint32_t rs = (par ? ~neg : neg) & (d >= 32 ? 0xFFFFFFFFu : (1u << d) - 1u);
-        if (g1 == 0) rs &= 1u << k1;
-        if (g2 == 0) rs &= ~(1u << k1);
-#pragma unroll
-        for (int j = 0; j < MAXDC; ++j)
-            if (j < d) {
-                const int mag = j == k1 ? g2 : g1;
-                const int r = (rs >> j) & 1 ? -mag : mag;
-                P[v[j]] = (signed char)min(max(x[j] + r, -Pmax), Pmax);
-            }
-        const uint32_t head = (uint32_t)g1 | (uint32_t)g2 << 6 | (uint32_t)k1 << 12;
-        if constexpr (RW == 2) {
-            rec[c * RW] = head;
-            rec[c * RW + 1] = rs;
-        } else {
-            rec[c] = head | rs << 16;
-        }
-    };
+    // The check with record c, degree d > 0 and variables v (layer_q_step, bp_layer_q.hpp)
+    const LayerQStep<MAXDC> step{P, rec, Q, Pmax, norm8, offset};
     // negative bytes of P word w (the padding bytes stay 0)
     auto neg_bytes = [&](int w) { return __builtin_popcount(Pw[w] & 0x80808080u); };
     // the first step of the next layer, loaded ahead of the barrier that ends this one (the index

@@ -268,6 +268,23 @@ BpPlan bp_layer_q_plan(const GraphShape &g, int B, int iters, int /*algo*/, bool
     const size_t lds = (mc ? curve_bytes(iters) : 0) + (((size_t)g.n + 3) & ~(size_t)3) +
                        layer_q_record_bytes(g.max_cdeg) * (size_t)g.m;
     if (lds > kLdsMax - 4096) return p;  // gmem_plan's budget; no slab form
+    if (g.qc_Z > 0) {
+        // a quasi-cyclic graph: bp_qc_q_kernel, one wave when a block row has no more checks
+        // than that (three of a 256-thread workgroup's four waves would only wait at barriers)
+        const int T = g.qc_Z <= 64 ? 64 : 256, D = g.max_cdeg <= 8 ? 8 : (g.max_cdeg <= 16 ? 16 : 32);
+        const auto *r = shapes::find(shapes::kQcQ, [&](const shapes::QcQ &s) { return s.T == T && s.maxdc == D; });
+        if (!r) return p;
+        static_assert((int)BpPath::QcQ256x32 - (int)BpPath::QcQ64x8 + 1 == sizeof(shapes::kQcQ) / sizeof(shapes::kQcQ[0]),
+                      "one BpPath per row of LDPC_QC_Q_SHAPES");
+        p.path = static_cast<BpPath>((int)BpPath::QcQ64x8 + (int)(r - shapes::kQcQ));
+        p.name = r->name;
+        p.threads = T;
+        p.grid = B;
+        p.lds = lds;
+        // informational: 32 wave slots of a CU, and kLdsMax bytes of LDS
+        p.wg_per_cu = (int)std::min<size_t>(32 / (T / 64), kLdsMax / lds);
+        return p;
+    }
     const int w = g.max_cdeg <= 8 ? 0 : (g.max_cdeg <= 16 ? 1 : 2);
     static const BpPath paths[3] = {BpPath::LayerQ8, BpPath::LayerQ16, BpPath::LayerQ32};
     static const char *const names[3] = {"bp_layer_q_kernel<8>", "bp_layer_q_kernel<16>", "bp_layer_q_kernel<32>"};

@@ -27,6 +27,8 @@ DropInCache g_dropin;
 // layout (tests run the other kernels on the same graphs), LDPC_NO_LOC_CHAIN=1 no chained layout
 // beside it (fixed-count sum-product decodes then run on the plain one), LDPC_LOC_T sets its thread count
 // (shape experiments); an explicit loc_T (ldpc_debug_loc_variant) goes over the environment's.
+// LDPC_NO_QC_KERNEL=1 keeps a quasi-cyclic graph's block-row schedule but not its row table
+// (qc_Z = 0): it decodes on the table kernels (tests and A/B runs hold bp_qc_q_kernel to them).
 LayoutOptions layout_options(int loc_T = 0) {
     LayoutOptions opt;
     const char *noloc = getenv("LDPC_NO_LOC_LAYOUT");
@@ -35,6 +37,8 @@ LayoutOptions layout_options(int loc_T = 0) {
     opt.loc_chain = !(nochain && nochain[0] == '1');
     if (const char *t = getenv("LDPC_LOC_T")) opt.loc_T = atoi(t);
     if (loc_T) opt.loc_T = loc_T;
+    const char *noqc = getenv("LDPC_NO_QC_KERNEL");
+    opt.qc_kernel = !(noqc && noqc[0] == '1');
     return opt;
 }
 }  // namespace
@@ -203,6 +207,18 @@ int ldpc_graph_create_csr(const int32_t *check_ptr, const int32_t *check_var, co
     LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
     return device_graph(h, out, true, layout_options());
 }
+
+int ldpc_graph_create_qc(int mb, int nb, int Z, const int32_t *base, ldpc_graph **out) {
+    LDPC_REQUIRE(out, "null output handle");
+    HostGraph h;
+    QcCode qc;
+    LDPC_TRY(host_graph_from_qc(mb, nb, Z, base, h, qc));
+    LayoutOptions opt = layout_options();
+    opt.qc = &qc;
+    return device_graph(h, out, true, opt);
+}
+
+const char *ldpc_graph_layer_rule(const ldpc_graph *g) { return g && g->lay_block_rows ? kQcLayerRule : kLayerRule; }
 
 void ldpc_graph_destroy(ldpc_graph *g) { destroy_device_graph(g); }
 
@@ -718,6 +734,50 @@ int ldpc_debug_layer_q_plan(const int32_t *check_ptr, const int32_t *check_var, 
                             char *names) {
     return graph_plans(check_ptr, check_var, var_ptr, var_slot, n, m, count, calls, cus, out, names, bp_layer_q_plan,
                        true, &BpPlan::wg_per_cu);
+}
+
+// --------------------------- quasi-cyclic codes, host only -----------------
+int ldpc_debug_qc_expand(int mb, int nb, int Z, const int32_t *base, int32_t *check_ptr, int32_t *check_var,
+                         int32_t *var_ptr, int32_t *var_slot, int32_t *layer) {
+    HostGraph h;
+    QcCode qc;
+    LDPC_TRY(host_graph_from_qc(mb, nb, Z, base, h, qc));
+    GraphShape g;
+    HostLayouts L;
+    LayoutOptions opt = layout_options();
+    opt.qc = &qc;
+    host_layouts(h, g, L, true, opt);
+    if (g.lay_L <= 0) {
+        set_error(kNoSchedule);
+        return LDPC_EUNSUP;
+    }
+    if (check_ptr) std::copy(h.cptr.begin(), h.cptr.end(), check_ptr);
+    if (check_var) std::copy(h.cvar.begin(), h.cvar.end(), check_var);
+    if (var_ptr) std::copy(h.vptr.begin(), h.vptr.end(), var_ptr);
+    if (var_slot) std::copy(h.vslot.begin(), h.vslot.end(), var_slot);
+    if (layer) std::copy(L.lay.layer.begin(), L.lay.layer.end(), layer);
+    return LDPC_OK;
+}
+
+int ldpc_debug_qc_plan(int mb, int nb, int Z, const int32_t *base, int count, const int32_t *calls, int cus,
+                       int64_t *out, char *names) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
+    HostGraph h;
+    QcCode qc;
+    LDPC_TRY(host_graph_from_qc(mb, nb, Z, base, h, qc));
+    GraphShape g;
+    HostLayouts L;
+    LayoutOptions opt = layout_options();
+    opt.qc = &qc;
+    host_layouts(h, g, L, true, opt);
+    if (g.lay_L <= 0) {
+        set_error(kNoSchedule);
+        return LDPC_EUNSUP;
+    }
+    return write_plans(count, calls, out, names, &BpPlan::wg_per_cu, nullptr,
+                       [&](int B, int iters, int algo, bool et, bool mc, bool want_post) {
+                           return bp_layer_q_plan(g, B, iters, algo, et, mc, want_post, cus);
+                       });
 }
 
 // --------------------------- random graphs / ensemble MC -------------------

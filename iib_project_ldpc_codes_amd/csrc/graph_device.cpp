@@ -25,7 +25,7 @@ hipError_t for_graph_arrays(ldpc_graph &g, const HostGraph &h, const HostLayouts
         {&g.chn_var, &L.chain.var},   {&g.chn_pos, &L.chain.pos},
         {&g.chn_info, &L.chain.info},
         {&g.lay_tab, &L.lay.tab},     {&g.lay_var, &L.lay.var},
-        {&g.lay_cbase, &L.lay.ptr},
+        {&g.lay_cbase, &L.lay.ptr},   {&g.qc_row, &L.qc_row},
     };
     for (const auto &a : arrays) {
         const hipError_t e = f(*a.first, *a.second);

@@ -287,21 +287,27 @@ bool build_irr_layout(const HostGraph &h, int &VPT, int &KC, int &DC, int &S, in
 // A change of either step changes every layered decode: it gets a new kLayerRule.
 const char *const kLayerRule = "first-fit/check-order+balance-to-mean/v1";
 
+// What every schedule needs of a graph: consistent lists, 1 <= check degree <= 32 everywhere, no
+// check holding a variable twice
+static bool layers_allowed(const HostGraph &h) {
+    if (!h.consistent || h.m <= 0 || h.max_cdeg > kLayerMaxD) return false;
+    std::vector<int32_t> row;
+    for (int c = 0; c < h.m; ++c) {
+        if (h.cptr[c + 1] == h.cptr[c]) return false;
+        row.assign(h.cvar.begin() + h.cptr[c], h.cvar.begin() + h.cptr[c + 1]);
+        std::sort(row.begin(), row.end());
+        if (std::adjacent_find(row.begin(), row.end()) != row.end()) return false;
+    }
+    return true;
+}
+
 bool build_layer_schedule(const HostGraph &h, LayerSchedule &S) {
     S = LayerSchedule();
     const int m = h.m, E = (int)h.cvar.size();
-    if (!h.consistent || m <= 0 || h.max_cdeg > kLayerMaxD) return false;
+    if (!layers_allowed(h)) return false;
     std::vector<int32_t> slot_check(E);
-    {
-        std::vector<int32_t> row;
-        for (int c = 0; c < m; ++c) {
-            if (h.cptr[c + 1] == h.cptr[c]) return false;
-            row.assign(h.cvar.begin() + h.cptr[c], h.cvar.begin() + h.cptr[c + 1]);
-            std::sort(row.begin(), row.end());
-            if (std::adjacent_find(row.begin(), row.end()) != row.end()) return false;
-            for (int s = h.cptr[c]; s < h.cptr[c + 1]; ++s) slot_check[s] = c;
-        }
-    }
+    for (int c = 0; c < m; ++c)
+        for (int s = h.cptr[c]; s < h.cptr[c + 1]; ++s) slot_check[s] = c;
     std::vector<int32_t> &layer = S.layer;
     layer.assign(m, -1);
     // check c fits layer l when no other check of its variables is there
@@ -339,6 +345,20 @@ bool build_layer_schedule(const HostGraph &h, LayerSchedule &S) {
         }
         if (!moved) break;
     }
+    layer_tables(h, S);
+    return true;
+}
+
+// The tables of a schedule whose layer[] is given (the colouring's above, a quasi-cyclic code's
+// block rows below): L, the layers' sizes, and chk / ptr / tab / var in (layer, falling degree,
+// id) order.  layer[c] in [0, L) with no layer empty and no two checks of a layer sharing a
+// variable is the caller's to ensure.
+void layer_tables(const HostGraph &h, LayerSchedule &S) {
+    const int m = h.m, E = (int)h.cvar.size();
+    const std::vector<int32_t> &layer = S.layer;
+    const int L = *std::max_element(layer.begin(), layer.end()) + 1;
+    std::vector<int> size(L, 0);
+    for (int c = 0; c < m; ++c) ++size[layer[c]];
     S.L = L;
     S.max_layer = *std::max_element(size.begin(), size.end());
     // (layer, falling degree, id) order, and the kernel's tables
@@ -360,7 +380,60 @@ bool build_layer_schedule(const HostGraph &h, LayerSchedule &S) {
             for (int q = S.ptr[l]; q < S.ptr[l + 1] && j < deg(S.chk[q]); ++q) S.var[w++] = h.cvar[h.cptr[S.chk[q]] + j];
         }
     }
-    return true;
+}
+
+// Quasi-cyclic codes.  The expansion convention is the header's (include/ldpc_mi355x.h,
+// ldpc_graph_create_qc): check r Z + i holds variable c Z + (i + s_rc) mod Z for every non-zero
+// cell of block row r, in ascending block-column order (the slot order); a variable's checks are
+// in ascending check id.
+const char *const kQcLayerRule = "qc/block-row/v1";
+
+int host_graph_from_qc(int mb, int nb, int Z, const int32_t *base, HostGraph &h, QcCode &qc) {
+    LDPC_REQUIRE(base && mb > 0 && nb > 0, "bad base matrix arguments");
+    LDPC_REQUIRE(Z >= 1, "quasi-cyclic code: need Z >= 1");
+    LDPC_REQUIRE((int64_t)mb * Z < (1 << 28) && (int64_t)nb * Z < (1 << 28), "quasi-cyclic code: too large");
+    std::vector<int> cdeg(nb, 0);
+    int64_t cells = 0;
+    qc = QcCode();
+    qc.row.assign((size_t)mb * kQcRow, 0);
+    for (int r = 0; r < mb; ++r) {
+        int32_t *row = &qc.row[(size_t)r * kQcRow];
+        int d = 0;
+        for (int c = 0; c < nb; ++c) {
+            const int s = base[(size_t)r * nb + c];
+            LDPC_REQUIRE(s >= -1 && s < Z, "quasi-cyclic code: a base entry is -1 (zero block) or a shift in [0, Z)");
+            if (s < 0) continue;
+            LDPC_REQUIRE(d < kLayerMaxD, "quasi-cyclic code: a block row has more than 32 non-zero blocks");
+            row[1 + 2 * d] = c * Z;
+            row[2 + 2 * d] = s;
+            ++d;
+            ++cdeg[c];
+        }
+        LDPC_REQUIRE(d > 0, "quasi-cyclic code: an all-zero block row");
+        row[0] = d;
+        cells += d;
+    }
+    for (int c = 0; c < nb; ++c) LDPC_REQUIRE(cdeg[c] > 0, "quasi-cyclic code: an all-zero block column");
+    LDPC_REQUIRE(cells * Z < (1 << 30), "quasi-cyclic code: too many edges");
+    qc.Z = Z; qc.mb = mb; qc.nb = nb;
+    const int n = nb * Z, m = mb * Z, E = (int)(cells * Z);
+    std::vector<int32_t> cptr(m + 1, 0), cvar(E), vptr(n + 1, 0), vslot(E);
+    for (int r = 0; r < mb; ++r) {
+        const int32_t *row = &qc.row[(size_t)r * kQcRow];
+        for (int i = 0; i < Z; ++i) {
+            const int c = r * Z + i, e0 = cptr[c];
+            cptr[c + 1] = e0 + row[0];
+            for (int j = 0; j < row[0]; ++j) {
+                const int v = row[1 + 2 * j] + (i + row[2 + 2 * j]) % Z;
+                cvar[e0 + j] = v;
+                ++vptr[v + 1];
+            }
+        }
+    }
+    for (int v = 0; v < n; ++v) vptr[v + 1] += vptr[v];
+    std::vector<int32_t> fill(vptr.begin(), vptr.end() - 1);
+    for (int e = 0; e < E; ++e) vslot[fill[cvar[e]]++] = e;  // slots ascend with the check id
+    return host_graph_from_csr(cptr.data(), cvar.data(), vptr.data(), vslot.data(), n, m, h);
 }
 
 void host_layouts(const HostGraph &h, GraphShape &g, HostLayouts &L, bool layouts, const LayoutOptions &opt) {
@@ -419,7 +492,23 @@ void host_layouts(const HostGraph &h, GraphShape &g, HostLayouts &L, bool layout
             L.irr_cdeg.clear();
         }
     }
-    if (build_layer_schedule(h, L.lay)) {
+    if (opt.qc && opt.qc->Z > 0 && layers_allowed(h)) {
+        // a quasi-cyclic code: the block rows are the layers (a block row has at most one
+        // circulant per block column, so its Z checks share no variable); all degrees of a block
+        // row are equal, so the tables' order is the check order and ptr[l] = l Z
+        const QcCode &qc = *opt.qc;
+        L.lay = LayerSchedule();
+        L.lay.layer.resize(h.m);
+        for (int c = 0; c < h.m; ++c) L.lay.layer[c] = c / qc.Z;
+        layer_tables(h, L.lay);
+        g.lay_L = L.lay.L;
+        g.lay_max = L.lay.max_layer;
+        g.lay_block_rows = true;
+        if (opt.qc_kernel) {
+            L.qc_row = qc.row;
+            g.qc_Z = qc.Z; g.qc_mb = qc.mb; g.qc_nb = qc.nb;
+        }
+    } else if (build_layer_schedule(h, L.lay)) {
         g.lay_L = L.lay.L;
         g.lay_max = L.lay.max_layer;
     }

@@ -36,6 +36,24 @@ struct LayerSchedule {
     std::vector<int32_t> layer, ptr, chk, tab, var;
 };
 bool build_layer_schedule(const HostGraph &h, LayerSchedule &S);
+// The tables of a schedule whose S.layer is given (every layer in use, no two checks of a layer
+// sharing a variable): S.L, S.max_layer, ptr, chk, tab, var.  build_layer_schedule ends in it.
+void layer_tables(const HostGraph &h, LayerSchedule &S);
+
+// A quasi-cyclic code: H is an mb x nb array of Z x Z circulant permutations or zero blocks,
+// base[r][c] = -1 for a zero block, otherwise the shift 0 <= s < Z.  Expansion (the header's,
+// ldpc_graph_create_qc): check r Z + i holds variable c Z + (i + s_rc) mod Z for every non-zero
+// cell of block row r, in ascending block-column order (the slot order); a variable's checks are
+// in ascending check id.  The block rows are the layers (kQcLayerRule).
+// row [mb][kQcRow]: bp_qc_q_kernel's table (ldpc_internal.hpp).
+extern const char *const kQcLayerRule;
+struct QcCode {
+    int Z = 0, mb = 0, nb = 0;
+    std::vector<int32_t> row;
+};
+// Validates (LDPC_EINVAL: Z < 1, a shift outside [0, Z), an all-zero block row or column, a
+// block-row degree above 32) and expands.
+int host_graph_from_qc(int mb, int nb, int Z, const int32_t *base, HostGraph &h, QcCode &qc);
 
 // The soft-decoder layouts of a graph, built on the host: the arrays device_graph uploads.
 struct HostLayouts {
@@ -43,12 +61,15 @@ struct HostLayouts {
     LocLayout loc;
     LocChainLayout chain;
     LayerSchedule lay;
+    std::vector<int32_t> qc_row;  // QcCode::row of a quasi-cyclic graph that runs bp_qc_q_kernel
 };
 
 struct LayoutOptions {
     bool loc_layout = true;  // build the local-edge layout (off: tests run the other kernels on the same graphs)
     int loc_T = 0;           // threads of the local-edge layout, 0 = the shipped choice
     bool loc_chain = true;   // build the chained layout beside it (off: tests and A/B runs of the plain one)
+    const QcCode *qc = nullptr;  // the graph is this quasi-cyclic code's expansion: its block rows are the layers
+    bool qc_kernel = true;       // ... and it runs bp_qc_q_kernel (off: the table kernels on the block-row schedule)
 };
 
 // Fills g and, with layouts, the kernels' layouts (L and the lane_* / irr_* / loc_* scalars of g).

@@ -101,6 +101,14 @@ struct LayerQArgs {
     int32_t *trial;  // [B][max_iters+1]
 };
 
+// bp_qc_q_kernel: bp_layer_q_kernel's call and quantiser (q; its tab / var / cbase are not read, L
+// is the number of block rows) and the quasi-cyclic code's row table (ldpc_graph::qc_row)
+struct QcQArgs {
+    LayerQArgs q;
+    const int32_t *row;  // [L][kQcRow]: degree, then (column base, shift) per edge
+    int Z;
+};
+
 // gb_kernel (gb.hip): Gallager A/B on bit planes
 struct GbArgs {
     const int32_t *cptr, *cvar, *vptr, *vslot;
@@ -145,6 +153,8 @@ hipError_t launch_generic(const BpPlan &p, const ldpc_graph &g, BpArgs a, int al
 hipError_t launch_layer(const BpPlan &p, LayerArgs a, int algo, bool et, bool mc, hipStream_t s);
 // bp_layer_q_kernel (bp_layer_q.hip), from a bp_layer_q_plan
 hipError_t launch_layer_q(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s);
+// bp_qc_q_kernel (bp_qc_q.hip), from a bp_layer_q_plan of a quasi-cyclic graph
+hipError_t launch_qc_q(const BpPlan &p, const QcQArgs &a, bool et, bool mc, hipStream_t s);
 // Ensemble BEC Monte-Carlo by frontier peeling (peel.hip): launch_mc_bec_ensemble's BecKernel::Peel
 // plans; trial b decodes on the (dv, dc) regular graph b of the two lists.
 hipError_t launch_mc_bec_peel(const BecPlan &plan, int n, int m, int dv, int dc, const int32_t *check_lookup,

@@ -41,6 +41,9 @@
     X(true, csr, uint16_t, u16) X(true, csr, int, int) X(false, regular, uint16_t, u16) X(false, regular, int, int)
 // sample_var_side_kernel (sampler.hip): threads, staged row entry, its tag
 #define LDPC_SAMPLE_VAR_SIDE_SHAPES(X) X(1024, uint16_t, u16) X(1024, int32_t, int32)
+// bp_qc_q_kernel (bp_qc_q.hip): threads, widest block-row degree; each in the four (early stop,
+// Monte-Carlo) modes.  Row i is BpPath::QcQ64x8 + i (ldpc_internal.hpp lists them in this order).
+#define LDPC_QC_Q_SHAPES(X) X(64, 8) X(64, 16) X(64, 32) X(256, 8) X(256, 16) X(256, 32)
 
 namespace ldpc {
 namespace shapes {
@@ -54,6 +57,7 @@ struct Shape2 { int T, per_thread; };  // bp_lds: VPT; bp_loc: KP
 struct SampleLevel { int K; bool lds; const char *name; };
 struct SampleSeq { bool csr; int ring; const char *seq, *search; };
 struct SampleVarSide { int T, row; const char *name; };
+struct QcQ { int T, maxdc; const char *name; };
 
 #define LDPC_ROW(T, W, P, TAG) \
     {T, W, (int)sizeof(P), "bec_dec_bits_kernel<" #T "," #W "," #TAG ">", "bec_mc_bits_kernel<" #T "," #W "," #TAG ">"},
@@ -86,6 +90,9 @@ constexpr SampleSeq kSampleSeq[] = {LDPC_SAMPLE_SEQ_SHAPES(LDPC_ROW)};
 #undef LDPC_ROW
 #define LDPC_ROW(T, IDX, TAG) {T, (int)sizeof(IDX), "sample_var_side_kernel<" #T "," #TAG ">"},
 constexpr SampleVarSide kSampleVarSide[] = {LDPC_SAMPLE_VAR_SIDE_SHAPES(LDPC_ROW)};
+#undef LDPC_ROW
+#define LDPC_ROW(T, D) {T, D, "bp_qc_q_kernel<" #T "," #D ">"},
+constexpr QcQ kQcQ[] = {LDPC_QC_Q_SHAPES(LDPC_ROW)};
 #undef LDPC_ROW
 
 // The first row of `rows` that `match` accepts, nullptr when there is none

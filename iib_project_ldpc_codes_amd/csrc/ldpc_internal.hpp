@@ -44,6 +44,11 @@ struct GraphShape {
     // Layer schedule of bp_layer_kernel (build_layer_schedule, graph_host.cpp): lay_L layers, the
     // largest of lay_max checks; lay_L == 0: none
     int lay_L = 0, lay_max = 0;
+    // Quasi-cyclic graph (host_graph_from_qc): its layers are its block rows (kQcLayerRule), not a
+    // colouring; qc_Z > 0: the mb x nb array of Z x Z blocks behind it, for bp_qc_q_kernel's
+    // row table (qc_row).  0 for every other graph, and for a quasi-cyclic one kept on the table kernels.
+    bool lay_block_rows = false;
+    int qc_Z = 0, qc_mb = 0, qc_nb = 0;
 };
 
 // Device-resident Tanner graph: the shape and the device arrays (listed once more, each with the
@@ -71,6 +76,7 @@ struct ldpc_graph : GraphShape {
     // lay_var [E] variables, layer-ordered and lane-major
     int32_t *lay_tab = nullptr, *lay_var = nullptr;
     int32_t *lay_cbase = nullptr;  // [L+1] checks before each layer (LayerSchedule::ptr): bp_layer_q_kernel's record base
+    int32_t *qc_row = nullptr;     // [qc_mb][kQcRow] degree and (column base, shift) pairs of each block row (qc_Z > 0)
 };
 
 // Local-edge layout (loc_layout.cpp): see the comment there.
@@ -265,7 +271,9 @@ enum class BpPath {
     // bp_layer_kernel (bp_layer_plan only)
     Layer8, Layer16, Layer32, LayerG8, LayerG16, LayerG32,
     // bp_layer_q_kernel (bp_layer_q_plan only)
-    LayerQ8, LayerQ16, LayerQ32
+    LayerQ8, LayerQ16, LayerQ32,
+    // bp_qc_q_kernel<T,MAXDC> (bp_layer_q_plan on a quasi-cyclic graph), in the order of LDPC_QC_Q_SHAPES
+    QcQ64x8, QcQ64x16, QcQ64x32, QcQ256x8, QcQ256x16, QcQ256x32
 };
 struct BpPlan {
     BpPath path = BpPath::None;
@@ -307,6 +315,8 @@ BpPlan bp_layer_plan(const GraphShape &g, int B, int iters, int algo, bool early
 // (layer_q_record_bytes: 4 bytes up to check degree 16, 8 up to 32) wholly in LDS.  There is no
 // slab form: a block past gmem_plan's budget (160 KiB - 4 KiB) has no plan (BpPath::None), as has
 // a graph without a layer schedule.  wg_per_cu: how many such workgroups one CU holds.
+// A quasi-cyclic graph (qc_Z > 0) goes to bp_qc_q_kernel<T,MAXDC> (bp_qc_q.hip) with the same block,
+// LDS formula and cap: T = 64 (one wave) when Z <= 64, else 256; MAXDC by the largest block-row degree.
 BpPlan bp_layer_q_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
                        int cus);
 constexpr size_t layer_q_record_bytes(int max_cdeg) { return max_cdeg <= 16 ? 4 : 8; }
@@ -316,6 +326,9 @@ constexpr size_t layer_block_bytes(size_t n, size_t E) { return pad16((n + E) * 
 // exactly when p < [j + 1] - [j] (and [1] - [0] is the layer's number of checks); [32] is the
 // layer's end, the next row's [0].
 constexpr int kLayerMaxD = 32, kLayerTab = kLayerMaxD + 1;
+// Row r of qc_row (a quasi-cyclic code's block row r): [0] its degree d, then per edge j < d, in
+// ascending block-column order, [1 + 2 j] the column base c Z and [2 + 2 j] the shift (0 past d).
+constexpr int kQcRow = 1 + 2 * kLayerMaxD;
 constexpr size_t ens_block_bytes(size_t n, size_t E) { return pad16(E * 8 + n * 4); }
 // bp_generic_kernel's block: messages float[E] | channel LLRs float[n] | decision bytes u8[E]
 constexpr size_t generic_block_bytes(size_t n, size_t E) { return pad16(E * 5 + n * 4); }
@@ -384,7 +397,7 @@ struct LayerFamily {  // layered (row-serial) schedule of graph_host.cpp's build
     }
     hipError_t launch(const BpPlan &p, const SoftCall &c, float *scratch, hipStream_t s) const;
 };
-struct LayerQFamily {  // fixed-point layered min-sum (bp_layer_q.hip); q validated by the caller; no scratch
+struct LayerQFamily {  // fixed-point layered min-sum (bp_layer_q.hip, bp_qc_q.hip); q validated by the caller; no scratch
     const ldpc_graph &g;
     const ldpc_quant &q;
     BpPlan plan(const SoftCall &c, int cus) const {

@@ -23,8 +23,11 @@ CHANNELS = {"bec": CH_BEC, "bsc": CH_BSC, "awgn": CH_AWGN, "biawgn": CH_AWGN,
 SCHEDULES = ("flooding", "layered")
 
 
-def layer_rule():
-    """Name of the rule that colours a graph's checks into layers (snapshot.LAYER_RULE)."""
+def layer_rule(graph=None):
+    """Name of the rule that colours a graph's checks into layers (snapshot.LAYER_RULE); with a
+    graph, the rule that gave that graph its layers (a quasi-cyclic code's: "qc/block-row/v1")."""
+    if graph is not None and hasattr(graph, "layer_rule"):
+        return graph.layer_rule
     return _native.lib().ldpc_layer_rule().decode()
 
 

@@ -65,7 +65,8 @@ def config(mc):
            "early_stop": bool(mc.early_stop), "expurgation": int(mc.expurgation),
            "optimal": bool(mc.optimal), "message_passing": bool(mc.message_passing)}
     if getattr(mc, "schedule", "flooding") == "layered":  # flooding snapshots stay as they always were
-        cfg.update({"schedule": "layered", "layer_rule": LAYER_RULE})
+        # a quasi-cyclic graph's layers are its block rows (qc.LAYER_RULE), every other graph's the colouring's
+        cfg.update({"schedule": "layered", "layer_rule": getattr(mc.graph, "layer_rule", LAYER_RULE)})
     if getattr(mc, "quant", None) is not None:  # the fixed-point decoder: only then, so every other config is unchanged
         cfg["quant"] = mc.quant.as_dict()
     if getattr(mc, "gallager", False):  # Gallager A/B: only then, as above (alpha is not read: recorded as it was given)

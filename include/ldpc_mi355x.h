@@ -109,6 +109,31 @@ int ldpc_graph_create(const int32_t *variable_to_check_list, const int32_t *chec
 int ldpc_graph_create_csr(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
                           const int32_t *var_slot, int n, int m, ldpc_graph **out);
 
+/*
+ * Upload a quasi-cyclic code: H is an mb x nb array of Z x Z blocks, base int32[mb][nb] (row-major)
+ * holding -1 for a zero block, otherwise the shift 0 <= s < Z of a circulant permutation.
+ *
+ * Expansion convention (stated here once; everything else restates it): check r Z + i holds
+ * variable c Z + (i + s_rc) mod Z for every non-zero cell (r, c) of block row r, in ascending
+ * block-column order -- that order is the check's slot order, so it fixes the "first index" i1 of
+ * the fixed-point contract below.  A variable's checks are in ascending check id.
+ *
+ * LDPC_EINVAL: Z < 1, a shift outside [0, Z), an all-zero block row or block column, a block row
+ * with more than 32 non-zero blocks.
+ *
+ * The graph is an ordinary graph to every decoder, the encoder and the samplers' consumers.  Its
+ * layer schedule is not a colouring: a block row has at most one circulant per block column, so
+ * its Z checks share no variable, and layer[check] = check / Z (rule "qc/block-row/v1",
+ * ldpc_graph_layer_rule).  "(layer, check id) order" in the layered contracts is then plain check
+ * order.  The fixed-point layered entries run bp_qc_q_kernel (csrc/bp_qc_q.hip) on it, which forms
+ * the variables of a check from the block row's shifts; with LDPC_NO_QC_KERNEL=1 in the
+ * environment at creation the graph keeps the block-row schedule and decodes on the table kernels.
+ */
+int ldpc_graph_create_qc(int mb, int nb, int Z, const int32_t *base, ldpc_graph **out);
+/* The name of the rule that gave this graph its layers: "qc/block-row/v1" for a graph of
+ * ldpc_graph_create_qc, ldpc_layer_rule() otherwise. */
+const char *ldpc_graph_layer_rule(const ldpc_graph *g);
+
 void ldpc_graph_destroy(ldpc_graph *g);
 int ldpc_graph_info(const ldpc_graph *g, int32_t *n, int32_t *m, int32_t *num_edges);
 
@@ -681,6 +706,23 @@ int ldpc_debug_layer_q_plan(const int32_t *check_ptr, const int32_t *check_var, 
                             int64_t *out, char *names);
 /* Host-only: LDPC_OK for a valid parameter set (the rules above), else LDPC_EINVAL. */
 int ldpc_quant_check(const ldpc_quant *q);
+
+/*
+ * Host-only: the expansion of a quasi-cyclic code (ldpc_graph_create_qc's arguments and
+ * convention) as the four CSR arrays of ldpc_graph_create_csr -- check_ptr int32[mb Z + 1],
+ * check_var and var_slot int32[E] (E = Z x the number of non-zero cells), var_ptr
+ * int32[nb Z + 1] -- and layer int32[mb Z], the block row of every check.  Any may be NULL.
+ */
+int ldpc_debug_qc_expand(int mb, int nb, int Z, const int32_t *base, int32_t *check_ptr, int32_t *check_var,
+                         int32_t *var_ptr, int32_t *var_slot, int32_t *layer);
+/*
+ * Host-only: the launch plans of `count` fixed-point layered calls on a quasi-cyclic code; calls /
+ * out / names as ldpc_debug_layer_q_plan, names bp_qc_q_kernel<64|256,8|16|32>: 64 threads (one
+ * wave) when Z <= 64, else 256; the width by the largest block-row degree; the same LDS formula
+ * and cap.  Under LDPC_NO_QC_KERNEL=1 the rows are bp_layer_q_kernel's on the block-row schedule.
+ */
+int ldpc_debug_qc_plan(int mb, int nb, int Z, const int32_t *base, int count, const int32_t *calls, int cus,
+                       int64_t *out, char *names);
 
 /*
  * Host-only: the launch plans of `count` BEC erasure-decoding calls on a graph of n variables

@@ -7,9 +7,12 @@
         trial, parallel_simulator_expurgated.py), n=64800, BEC, 200 it, expurgation X=3;
         --channel bsc|awgn [--algo minsum|spa]: the same ensemble under soft decoding (50 it,
         early stop, no expurgation unless --expurgation is given)
---schedule layered (cfg3, cfg4): the row-serial schedule of hardware decoders on the fixed code
+  qc:   a quasi-cyclic code the user brings (--base FILE --Z Z: whitespace-separated rows of shifts,
+        -1 for a zero block) or an array code (--array dv,dc,Z: shift r c mod Z, Z prime), BSC,
+        min-sum, 50 it; its layers are its block rows, and --quant runs bp_qc_q_kernel
+--schedule layered (cfg3, cfg4, qc): the row-serial schedule of hardware decoders on the fixed code
 (decoder.bp_decode_dev; the ensemble has no layered form).
---quant bits,post_bits,scale,norm8,offset (cfg3 with --schedule layered): the fixed-point layered
+--quant bits,post_bits,scale,norm8,offset (cfg3 / qc with --schedule layered): the fixed-point layered
 min-sum (decoder.Quant) -- what frame error rate a q-bit hardware decoder reaches.
 --algo gallager [--flip-threshold b] (cfg3): Gallager A (b = 0) / B hard-decision decoding on the same
 code and crossover points (decoder.gallager_decode_dev), to set beside min-sum.
@@ -29,6 +32,8 @@ parallel_simulator.py:198), --trials, or --seconds.
   python scripts/fer_sweep.py cfg3 --schedule layered --quant 5,7,2.0,6,0 --points 0.07
   python scripts/fer_sweep.py cfg3 --algo gallager --points 0.038,0.035,0.03
   python scripts/fer_sweep.py cfg3 --schedule layered --quant 5,7,2.0,8,1 --codewords random --points 0.06
+  python scripts/fer_sweep.py qc --array 3,6,1667 --schedule layered --quant 6,8,2.0,6,0 --points 0.05
+  python scripts/fer_sweep.py qc --base table.txt --Z 81 --schedule layered --points 0.04
 """
 import argparse
 import json
@@ -61,7 +66,10 @@ def parse_quant(text):
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["cfg3", "cfg4", "ens"])
+    ap.add_argument("config", choices=["cfg3", "cfg4", "ens", "qc"])
+    ap.add_argument("--base", type=str, default=None, help="qc: the base matrix file (qc.QCCode.from_text), with --Z")
+    ap.add_argument("--Z", type=int, default=None, help="qc: the circulant size of --base")
+    ap.add_argument("--array", type=str, default=None, metavar="DV,DC,Z", help="qc: qc.array_code(dv, dc, Z)")
     ap.add_argument("--trials", type=int, default=1_000_000)
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--batch", type=int, default=None)
@@ -97,8 +105,15 @@ def parse(argv=None):
         args.expurgation = 3 if args.channel == "bec" else -1
     if args.schedule == "layered" and args.config == "ens":
         ap.error("--schedule layered needs a fixed code (cfg3, cfg4): no host-built schedule per sampled graph")
-    if args.quant is not None and (args.schedule != "layered" or args.config != "cfg3"):
-        ap.error("--quant needs cfg3 (min-sum) with --schedule layered")
+    if args.quant is not None and (args.schedule != "layered" or args.config not in ("cfg3", "qc")):
+        ap.error("--quant needs cfg3 or qc (min-sum) with --schedule layered")
+    if args.config == "qc":
+        if (args.array is None) == (args.base is None) or (args.base is not None and args.Z is None):
+            ap.error("qc needs --base FILE --Z Z, or --array dv,dc,Z")
+        if args.array is not None and len(args.array.split(",")) != 3:
+            ap.error("--array takes dv,dc,Z")
+    elif args.base is not None or args.Z is not None or args.array is not None:
+        ap.error("--base, --Z and --array belong to qc")
     if args.algo == "gallager" and (args.config != "cfg3" or args.schedule != "flooding"):
         ap.error("--algo gallager needs cfg3 with the flooding schedule (a fixed code on the BSC)")
     if args.flip_threshold and args.algo != "gallager":
@@ -131,6 +146,14 @@ def main(argv=None):
         if args.algo == "gallager":  # below the Gallager A threshold 0.0395 (de.gallager_threshold)
             algo = "gallager"
             points = [float(p) for p in (args.points or "0.038,0.036,0.034,0.032,0.03").split(",")]
+    elif args.config == "qc":
+        from iib_project_ldpc_codes_amd import qc
+        code = (qc.array_code(*[int(x) for x in args.array.split(",")]) if args.array is not None
+                else qc.QCCode.from_text(args.base, args.Z))
+        g = code.graph()
+        channel, algo, alpha, iters = "bsc", "minsum", 0.75, 50
+        points = [float(p) for p in (args.points or "0.05,0.045,0.04,0.035,0.03").split(",")]
+        batch = args.batch or 65536
     elif args.config == "ens":
         g = None
         channel = args.channel
@@ -160,6 +183,9 @@ def main(argv=None):
         if args.checkpoint_dir:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
             tag = "" if args.schedule == "flooding" else "_" + args.schedule  # flooding keeps its file names
+            if args.config == "qc":  # one file per code
+                tag += "_" + (args.array.replace(",", "-") if args.array is not None
+                              else "%s-Z%d" % (os.path.basename(args.base), args.Z))
             if args.quant is not None:
                 q = args.quant
                 tag += "_q%d-%d-%g-%d-%d" % (q.bits, q.post_bits, q.scale, q.norm8, q.offset)
@@ -184,6 +210,8 @@ def main(argv=None):
                    "seconds": el, "codewords_per_s": (res["num_tests"] - trials0) / el}
             if args.schedule != "flooding":
                 out["schedule"] = args.schedule
+            if args.config == "qc":
+                out.update({"Z": g.code.Z, "base_rows": g.code.mb, "base_columns": g.code.nb})
             if args.quant is not None:
                 out["quant"] = args.quant.as_dict()
             if algo == "gallager":
