@@ -16,6 +16,7 @@ LDPC_EINVAL, LDPC_ENODEV, LDPC_EHIP, LDPC_ENOMEM, LDPC_EUNSUP = -1, -2, -3, -4, 
 CH_BEC, CH_BSC, CH_AWGN = 0, 1, 2
 ALGO_SPA, ALGO_MINSUM = 0, 1
 MC_NCOUNT = 4
+RM_TX, RM_PUNCT, RM_KNOWN = 0, 1, 2
 
 _lib = None
 
@@ -110,7 +111,13 @@ SIGNATURES = {
     "ldpc_info_bits_dev": ([u64, u64, i, i, P, P], i),
     "ldpc_channel_cw_dev": ([i, f, u64, u64, i, i, P, P, P], i),
     "ldpc_mc_cw_count_dev": ([P, P, i, P, P, i, i, i, i, i64, P, P], i),
-    "ldpc_debug_sample_plan": ([i, i, i, i, i, i, i, i, i, P, P], i),
+    "ldpc_rate_match_create": ([i, P, P, ct.POINTER(P)], i),
+    "ldpc_rate_match_destroy": ([P], None),
+    "ldpc_rate_match_info": ([P, P, P, P, P, P], i),
+    "ldpc_channel_rm_dev": ([P, i, f, f, u64, u64, i, P, P, P], i),
+    "ldpc_mc_rm_count_dev": ([P, P, P, i, P, P, i, i, i, i64, P, P], i),
+    "ldpc_debug_rate_match_pack": ([i, P, P, P, P], i),
+    "ldpc_debug_sample_plan":([i, i, i, i, i, i, i, i, i, P, P], i),
     "ldpc_sample_csr_dev": ([i, i, P, P, u64, u64, i, P, P, P, P], i),
     "ldpc_sample_csr": ([i, i, P, P, u64, u64, i, P, P, P], i),
     "ldpc_ml_decode_batch_dev": ([P, P, i, P, P, P], i),

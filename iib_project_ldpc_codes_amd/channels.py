@@ -4,7 +4,8 @@ Host methods keep the reference's numpy behaviour for per-trial callers;
 ``device_outputs`` generates a whole batch on the MI355X (Philox4x32-10,
 counter = (codeword, variable), see ldpc_channel_dev) so Monte-Carlo never
 round-trips channel noise through the host.  ``codewords=`` transmits the given 0/1 words instead of
-the all-zero codeword (the same noise stream, reflected: ldpc_channel_cw_dev).
+the all-zero codeword (the same noise stream, reflected: ldpc_channel_cw_dev); ``rate_match=`` leaves
+the punctured and known positions of a ratematch.RateMatch out (ldpc_channel_rm_dev).
 """
 import numpy as np
 
@@ -33,8 +34,9 @@ class BEC:
         random_vector = np.random.rand(len(input_binary))
         return np.where(random_vector < self.erasure_prob, 2, input_binary)
 
-    def device_outputs(self, seed, first_cw, n, B, out=None, codewords=None):
-        return decoder.channel_dev(CH_BEC, self.erasure_prob, seed, first_cw, n, B, out, codewords=codewords)
+    def device_outputs(self, seed, first_cw, n, B, out=None, codewords=None, rate_match=None, known_llr=1024.0):
+        return decoder.channel_dev(CH_BEC, self.erasure_prob, seed, first_cw, n, B, out, codewords=codewords,
+                                   rate_match=rate_match, known_llr=known_llr)
 
 
 class BSC:
@@ -59,8 +61,9 @@ class BSC:
         lc = self.llr_magnitude()
         return np.where(np.asarray(received) == 1, -lc, lc).astype(np.float32)
 
-    def device_outputs(self, seed, first_cw, n, B, out=None, codewords=None):
-        return decoder.channel_dev(CH_BSC, self.crossover_prob, seed, first_cw, n, B, out, codewords=codewords)
+    def device_outputs(self, seed, first_cw, n, B, out=None, codewords=None, rate_match=None, known_llr=1024.0):
+        return decoder.channel_dev(CH_BSC, self.crossover_prob, seed, first_cw, n, B, out, codewords=codewords,
+                                   rate_match=rate_match, known_llr=known_llr)
 
 
 class BIAWGN:
@@ -85,5 +88,6 @@ class BIAWGN:
     def llr(self, y):
         return (2.0 / self.sigma ** 2 * np.asarray(y)).astype(np.float32)
 
-    def device_outputs(self, seed, first_cw, n, B, out=None, codewords=None):
-        return decoder.channel_dev(CH_AWGN, self.sigma, seed, first_cw, n, B, out, codewords=codewords)
+    def device_outputs(self, seed, first_cw, n, B, out=None, codewords=None, rate_match=None, known_llr=1024.0):
+        return decoder.channel_dev(CH_AWGN, self.sigma, seed, first_cw, n, B, out, codewords=codewords,
+                                   rate_match=rate_match, known_llr=known_llr)

@@ -15,6 +15,7 @@
 
 #include "encode_host.hpp"
 #include "graph_device.hpp"
+#include "rate_match_host.hpp"
 #include "workspace.hpp"
 
 namespace ldpc {
@@ -1270,6 +1271,78 @@ int ldpc_mc_cw_count_dev(const uint8_t *d_cw, const void *d_chan, int chan_is_ll
     int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *cut = ws.cutoff.get<int32_t>(4);
     LDPC_ALLOCATED(trial && cut);
     LDPC_HIP(launch_cw_count(d_cw, d_chan, chan_is_llr != 0, d_hard, n, B, max_iters, trial, s));
+    LDPC_HIP(launch_mc_reduce(trial, d_its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
+    return LDPC_OK;
+}
+
+// --------------------------- rate matching (rate_match_host.cpp, rate_match.hip) -----------------
+int ldpc_rate_match_create(int n, const uint8_t *cls, const uint8_t *count, ldpc_rate_match **out) {
+    LDPC_REQUIRE(out, "null output handle");
+    RateMatchDesc d;
+    LDPC_TRY(rate_match_pack(n, cls, count, d));
+    LDPC_TRY(require_device());
+    std::unique_ptr<ldpc_rate_match, void (*)(ldpc_rate_match *)> rm(new ldpc_rate_match(), ldpc_rate_match_destroy);
+    rm->n = d.n, rm->n_tx = d.n_tx, rm->n_punct = d.n_punct, rm->n_known = d.n_known, rm->n_count = d.n_count;
+    (void)hipGetDevice(&rm->device);
+    LDPC_HIP(hipMalloc(reinterpret_cast<void **>(&rm->desc), d.packed.size()));
+    LDPC_HIP(hipMemcpy(rm->desc, d.packed.data(), d.packed.size(), hipMemcpyHostToDevice));
+    *out = rm.release();
+    return LDPC_OK;
+}
+
+void ldpc_rate_match_destroy(ldpc_rate_match *rm) {
+    if (!rm) return;
+    (void)hipFree(rm->desc);
+    delete rm;
+}
+
+int ldpc_rate_match_info(const ldpc_rate_match *rm, int32_t *n, int32_t *n_tx, int32_t *n_punct, int32_t *n_known,
+                         int32_t *n_count) {
+    LDPC_REQUIRE(rm, "null rate-matching description");
+    if (n) *n = rm->n;
+    if (n_tx) *n_tx = rm->n_tx;
+    if (n_punct) *n_punct = rm->n_punct;
+    if (n_known) *n_known = rm->n_known;
+    if (n_count) *n_count = rm->n_count;
+    return LDPC_OK;
+}
+
+int ldpc_debug_rate_match_pack(int n, const uint8_t *cls, const uint8_t *count, uint8_t *packed, int32_t *info) {
+    RateMatchDesc d;
+    LDPC_TRY(rate_match_pack(n, cls, count, d));
+    if (packed) std::copy(d.packed.begin(), d.packed.end(), packed);
+    if (info) info[0] = d.n, info[1] = d.n_tx, info[2] = d.n_punct, info[3] = d.n_known, info[4] = d.n_count;
+    return LDPC_OK;
+}
+
+int ldpc_channel_rm_dev(const ldpc_rate_match *rm, int channel, float param, float known_llr, uint64_t seed,
+                        uint64_t first_cw, int B, const uint8_t *d_cw, void *d_out, void *stream) {
+    LDPC_REQUIRE(rm, "null rate-matching description");
+    LDPC_REQUIRE((B == 0 || d_out) && B >= 0, "bad channel arguments");
+    LDPC_REQUIRE(std::isfinite(known_llr) && known_llr > 0.0f, "known_llr must be finite and > 0");
+    float p, p2;
+    LDPC_TRY(channel_params(channel, param, &p, &p2));
+    if (B == 0) return LDPC_OK;
+    LDPC_REQUIRE(((int64_t)B * ((rm->n + 3) / 4) + 255) / 256 <= 0x7fffffff, "B * n beyond one launch");
+    LDPC_HIP(launch_channel_rm(rm->desc, channel, p, p2, known_llr, seed, first_cw, rm->n, B, d_cw, d_out,
+                               static_cast<hipStream_t>(stream)));
+    return LDPC_OK;
+}
+
+int ldpc_mc_rm_count_dev(const ldpc_rate_match *rm, const uint8_t *d_cw, const void *d_chan, int chan_kind,
+                         const uint8_t *d_dec, const int32_t *d_its, int B, int max_iters, int expurgation,
+                         int64_t stop_frame_errors, int64_t *d_counters, void *stream) {
+    LDPC_REQUIRE(rm, "null rate-matching description");
+    LDPC_REQUIRE(d_counters && B >= 0 && max_iters >= 0, "bad MC arguments");
+    LDPC_REQUIRE(chan_kind >= 0 && chan_kind <= 2, "chan_kind must be 0 (BEC words), 1 (LLRs) or 2 (received bits)");
+    LDPC_REQUIRE(B == 0 || (d_chan && d_dec), "null channel outputs / decisions");
+    if (B == 0) return LDPC_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Workspace &ws = workspace(stream);  // this (device, stream)'s lock only, as ldpc_mc_cw_count_dev
+    std::lock_guard<std::mutex> wl(ws.mu);
+    int32_t *trial = ws.trial.get<int32_t>((size_t)B * (max_iters + 1)), *cut = ws.cutoff.get<int32_t>(4);
+    LDPC_ALLOCATED(trial && cut);
+    LDPC_HIP(launch_rm_count(rm->desc, d_cw, d_chan, chan_kind, d_dec, rm->n, B, max_iters, trial, s));
     LDPC_HIP(launch_mc_reduce(trial, d_its, B, max_iters, expurgation, stop_frame_errors, d_counters, cut, s));
     return LDPC_OK;
 }

@@ -15,8 +15,7 @@
 // encode_write_kernel: a thread owns four consecutive variables of one codeword, takes each from the
 //   info bytes or from its parity plane word (src[v]) and stores them as one dword (bytes when n is
 //   no multiple of 4 or the output is not 4-byte aligned).
-#include <rocrand/rocrand_kernel.h>
-
+#include "channel_cw.hpp"
 #include "device_common.hpp"
 #include "ldpc_internal.hpp"
 #include "ldpc_mi355x.h"
@@ -122,41 +121,15 @@ __global__ __launch_bounds__(256) void info_bits_kernel(uint32_t k0, uint32_t k1
 
 // channel_kernel (mc_kernels.hip) word for word, then the reflection where the codeword bit is 1:
 // the BEC keeps its erased positions and shows x elsewhere, the BSC and AWGN LLRs change sign.
+// The arithmetic is channel_cw.hpp's, shared with channel_rm_kernel (rate_match.hip).
 __global__ __launch_bounds__(256) void channel_cw_kernel(int kind, float p, float p2, uint64_t seed, uint64_t first_cw,
                                                          int n, int B, const uint8_t *__restrict__ cw, void *out) {
     const int groups = (n + 3) >> 2;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)groups * B) return;
-    const int b = (int)(idx / groups), g = (int)(idx % groups);
-    rocrand_state_philox4x32_10 st;
-    rocrand_init(seed, first_cw + (uint64_t)b, 4ull * (uint64_t)g, &st);
-    const uint4 r = rocrand4(&st);
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-    float val[4];
-    if (kind == 2) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float ua = u01(w[2 * h]), ub = u01(w[2 * h + 1]);
-            const float rad = sqrtf(-2.0f * logf(ua));
-            const float ang = 6.28318530717958647692f * ub;
-            val[2 * h] = (1.0f + p * (rad * cosf(ang))) * p2;
-            val[2 * h + 1] = (1.0f + p * (rad * sinf(ang))) * p2;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int v = 4 * g + i;
-        if (v >= n) break;
-        const size_t o = (size_t)b * n + v;
-        const float u = u01(w[i]);
-        const bool x = cw && (cw[o] & 1u);
-        if (kind == 0) {
-            static_cast<uint8_t *>(out)[o] = u < p ? 2 : (x ? 1 : 0);
-        } else {
-            const float llr = kind == 1 ? (u < p ? -p2 : p2) : val[i];
-            static_cast<float *>(out)[o] = x ? -llr : llr;
-        }
-    }
+    channel_cw_group(
+        kind, p, p2, seed, first_cw, n, groups, idx, cw, [&](int, size_t o, uint8_t word) { static_cast<uint8_t *>(out)[o] = word; },
+        [&](int, size_t o, float llr) { static_cast<float *>(out)[o] = llr; });
 }
 
 // One workgroup per trial: channel errors [llr < 0] != x (bits: bit 0 != x) and final errors hard != x

@@ -1,6 +1,6 @@
 // Internal declarations shared by the host files (capi.cpp, mc_run.cpp, graph_host.cpp, graph_device.cpp, loc_layout.cpp,
 // encode_host.cpp and the launch plans bp_plan.cpp, bec_plan.cpp, gb_plan.cpp, encode_plan.cpp, sample_plan.cpp) and the
-// kernels (bec.hip, peel.hip, gb.hip, encode.hip, bp_*.hip, mc_kernels.hip, ml.hip, sampler.hip).  Not part of the public
+// kernels (bec.hip, peel.hip, gb.hip, encode.hip, rate_match.hip, bp_*.hip, mc_kernels.hip, ml.hip, sampler.hip).  Not part of the public
 // ABI (see include/ldpc_mi355x.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -455,6 +455,13 @@ struct ldpc_encoder {
     int32_t *src = nullptr;                  // [n] information index j, or ~i of parity row i
 };
 
+// Device-resident rate-matching description (rate_match_host.hpp's, uploaded): the handle of the C
+// ABI's ldpc_rate_match_* entries.
+struct ldpc_rate_match {
+    int n = 0, n_tx = 0, n_punct = 0, n_known = 0, n_count = 0, device = 0;
+    uint8_t *desc = nullptr;  // [4 ceil(n / 4)] packed bytes
+};
+
 namespace ldpc {
 
 // The codeword family (encode.hip).  All asynchronous on `stream`.
@@ -470,6 +477,16 @@ hipError_t launch_channel_cw(int channel, float p, float p2, uint64_t seed, uint
 // errors against the codeword, the entries between them 0.
 hipError_t launch_cw_count(const uint8_t *d_cw, const void *d_chan, bool chan_is_llr, const uint8_t *d_hard, int n,
                            int B, int max_iters, int32_t *trial, hipStream_t stream);
+
+// Rate matching (rate_match.hip).  d_desc: the packed description (rate_match_host.hpp), 4-byte aligned.
+// launch_channel_rm: launch_channel_cw's outputs at the transmitted positions, +0 / the erasure at the
+// punctured ones, +-known_llr / the codeword bit at the known ones.
+hipError_t launch_channel_rm(const uint8_t *d_desc, int channel, float p, float p2, float known_llr, uint64_t seed,
+                             uint64_t first_cw, int n, int B, const uint8_t *d_cw, void *d_out, hipStream_t stream);
+// launch_cw_count's rows under the description's classes and count mask (d_cw nullptr: all-zero);
+// chan_kind 0: BEC words in d_chan and d_dec, 1: LLRs, 2: received bits.
+hipError_t launch_rm_count(const uint8_t *d_desc, const uint8_t *d_cw, const void *d_chan, int chan_kind,
+                           const uint8_t *d_dec, int n, int B, int max_iters, int32_t *trial, hipStream_t stream);
 
 // Buckets (= threads per workgroup) of the parallel graph sampler for n*dv
 // sockets; the permutation is in LDS (u16) when n*dv < 65536.  Must match

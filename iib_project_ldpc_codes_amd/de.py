@@ -15,9 +15,21 @@ from .ensembles import Ensemble
 # --------------------------------------------------------------------- BEC
 
 
-def bec_de(ens, eps, iterations, threshold=0.0):
+def _punctured_eps(eps, punctured):
+    """Erasure rate the decoder sees when a fraction `punctured` of the variables, chosen uniformly at
+    random, is not transmitted: a punctured variable arrives erased, so the channel is the BEC with
+    eps + pi - eps pi.  punctured = 0.0 returns eps itself."""
+    if not 0.0 <= punctured < 1.0:
+        raise ValueError(f"punctured must be a fraction in [0, 1), not {punctured!r}")
+    return eps + punctured - eps * punctured if punctured else eps
+
+
+def bec_de(ens, eps, iterations, threshold=0.0, punctured=0.0):
     """Erasure probability of v->c messages per iteration (starts with eps), in the
-    output convention of tools/density_evolution.py:9-16 (values <= threshold dropped)."""
+    output convention of tools/density_evolution.py:9-16 (values <= threshold dropped).
+    punctured: the fraction of variables not transmitted (_punctured_eps); the list then starts with
+    the erasure rate the decoder sees."""
+    eps = _punctured_eps(eps, punctured)
     out = [eps]
     x = eps
     for _ in range(iterations):
@@ -30,15 +42,18 @@ def bec_de(ens, eps, iterations, threshold=0.0):
     return out
 
 
-def bec_threshold(ens, iterations=100000, tol=1e-9, tolerance=1e-6):
-    """Largest eps whose DE falls below `tolerance` (bisection as test_de_threshold.py:55-66)."""
+def bec_threshold(ens, iterations=100000, tol=1e-9, tolerance=1e-6, punctured=0.0):
+    """Largest eps whose DE falls below `tolerance` (bisection as test_de_threshold.py:55-66).
+    punctured: the fraction of variables not transmitted (_punctured_eps) -- the threshold of the
+    channel's own erasure rate is then 1 - (1 - eps*) / (1 - punctured), eps* the unpunctured one."""
     lo, hi = 0.0, 1.0
     while hi - lo > tol:
         mid = 0.5 * (lo + hi)
+        seen = _punctured_eps(mid, punctured)
         x = 1.0
         ok = False
         for _ in range(iterations):
-            x = mid * ens.lam_poly(1.0 - ens.rho_poly(1.0 - x))
+            x = seen * ens.lam_poly(1.0 - ens.rho_poly(1.0 - x))
             if x < tolerance:
                 ok = True
                 break
@@ -169,6 +184,14 @@ def sigma_to_ebn0_db(sigma, rate):
 
 def regular(dv, dc):
     return Ensemble({dv: 1.0}, {dc: 1.0})
+
+
+def rate_matched_rate(K, n_tx, n_known):
+    """Rate of a rate-matched code (include/ldpc_mi355x.h): K - n_known information bits carried by
+    n_tx transmitted positions, K the dimension of the mother code."""
+    if n_tx <= 0 or not 0 <= n_known <= K:
+        raise ValueError("rate_matched_rate: need n_tx > 0 and 0 <= n_known <= K")
+    return (K - n_known) / n_tx
 
 
 # ------------------------------------------------- finite-length scaling (BEC)

@@ -312,16 +312,29 @@ def gallager_decode(graph, bits, max_iters, flip_threshold=0, early_stop=False):
 
 
 # ------------------------------------------------------------------ channels
-def channel_dev(kind, param, seed, first_cw, n, B, out=None, stream=None, device=None, codewords=None):
+def channel_dev(kind, param, seed, first_cw, n, B, out=None, stream=None, device=None, codewords=None,
+                rate_match=None, known_llr=1024.0):
     """Channel outputs for codewords first_cw..first_cw+B-1: BEC -> uint8 (0 / 1 / 2 erasure),
     BSC / AWGN -> float32 LLRs.  codewords=None: the all-zero codeword (ldpc_channel_dev);
     codewords: uint8 [B, n] device tensor of transmitted 0/1 words -- the same stream reflected where
-    the bit is 1 (ldpc_channel_cw_dev: the same erasures, LLRs exactly negated)."""
+    the bit is 1 (ldpc_channel_cw_dev: the same erasures, LLRs exactly negated).
+    rate_match: a ratematch.RateMatch (ldpc_channel_rm_dev) -- the transmitted positions as above, a
+    punctured one an erasure / +0.0, a known one its bit / +-known_llr."""
     torch = _torch()
     kind = CHANNELS[kind]
     if out is None:
         dt = torch.uint8 if kind == CH_BEC else torch.float32
         out = torch.empty((B, n), dtype=dt, device=device or "cuda")
+    if rate_match is not None:
+        rm = rate_match
+        if rm.n != n:
+            raise ValueError(f"the rate-matching description is of n = {rm.n}, the channel of n = {n}")
+        if codewords is not None:
+            assert codewords.dtype == torch.uint8 and codewords.is_contiguous() and tuple(codewords.shape) == (B, n)
+        rc = _native.lib().ldpc_channel_rm_dev(rm.handle(), kind, float(param), float(known_llr), int(seed),
+                                               int(first_cw), B, _ptr(codewords), out.data_ptr(), _stream(stream))
+        _native.check(rc, "ldpc_channel_rm_dev")
+        return out
     if codewords is not None:
         assert codewords.dtype == torch.uint8 and codewords.is_contiguous() and tuple(codewords.shape) == (B, n)
         rc = _native.lib().ldpc_channel_cw_dev(kind, float(param), int(seed), int(first_cw), n, B,

@@ -109,6 +109,74 @@ def codeword_executor(mc):
     return run
 
 
+def rate_match_executor(mc):
+    """Batch executor of rate_match=: the unfused chain of codeword_executor with the channel of
+    ldpc_channel_rm_dev and the counts of ldpc_mc_rm_count_dev.  BSC / BI-AWGN: [information bits ->
+    ratematch.shorten_info -> encode, with codewords="random" only; otherwise the entries get no
+    codeword and mean the all-zero one] -> rate-matched channel -> the configured decoder's device
+    decode entry -> counts under the description's count mask.  BEC (all-zero codeword): rate-matched
+    channel -> a copy of the words -> decoder.bec_decode_dev -> counts of the words still erased.
+    Buffers are kept per batch size."""
+    from . import decoder, ratematch
+    from .encoder import Encoder
+    torch = mc.torch
+    rm = mc.rate_match
+    random = mc.codewords == "random"
+    bec = mc.channel == CHANNELS["bec"]
+    enc = None
+    if random or rm.count == "info":
+        enc = getattr(mc.graph, "_encoder", None)  # one elimination per graph object, as codeword_executor
+        if enc is None:
+            enc = mc.graph._encoder = Encoder(mc.graph)
+        mc.encoder = enc
+        rm.bind(enc)
+    # a shortened parity position: ValueError here, not mid-run
+    short = ratematch.shortened_info_index(enc, rm) if random else None
+    n, K = mc.graph.n, (enc.K if random else 0)
+    bufs, short_dev = {}, {}
+
+    def run(first_cw, B, stop_frame_errors, counters, stream=None):
+        B = int(B)
+        if B <= 0:
+            return
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if B not in bufs:
+            dev = counters.device
+            u8 = dict(dtype=torch.uint8, device=dev)
+            bufs[B] = (torch.empty((B, K), **u8) if random else None, torch.empty((B, n), **u8) if random else None,
+                       torch.empty((B, n), dtype=torch.uint8 if bec else torch.float32, device=dev),
+                       torch.empty((B, n), **u8), torch.empty((B,), dtype=torch.int32, device=dev),
+                       torch.empty((B, mc.max_iters), dtype=torch.int32, device=dev) if bec else None)
+        info, cw, chan, dec, its, err = bufs[B]
+        with torch.cuda.stream(s):
+            if random:
+                enc.info_bits_dev(mc.seed, first_cw, B, out=info, stream=s)
+                if short.size:
+                    if info.device not in short_dev:  # the index tensor: uploaded once per device
+                        short_dev[info.device] = torch.as_tensor(short, device=info.device)
+                    ratematch.shorten_info(info, enc, rm, index=short_dev[info.device])
+                enc.encode_dev(info, out=cw, stream=s)
+            decoder.channel_dev(mc.channel, mc.param, mc.seed, first_cw, n, B, out=chan, stream=s, codewords=cw,
+                                rate_match=rm, known_llr=mc.known_llr)
+            if bec:
+                dec.copy_(chan)
+                err.zero_()
+                decoder.bec_decode_dev(mc.graph, dec, mc.max_iters, errors=err, its=its, stream=s)
+            elif mc.gallager:  # a known position arrives as y = x: llr = +-known_llr
+                bits = (chan < 0).to(torch.uint8)
+                decoder.gallager_decode_dev(mc.graph, bits, mc.max_iters, mc.flip_threshold, mc.early_stop, hard=dec,
+                                            its=its, stream=s)
+            else:
+                decoder.bp_decode_dev(mc.graph, chan, mc.max_iters, mc.algo, mc.alpha, mc.early_stop, hard=dec, its=its,
+                                      stream=s, want_post=False, schedule=mc.schedule, quant=mc.quant)
+        rc = _native.lib().ldpc_mc_rm_count_dev(rm.handle(), None if cw is None else cw.data_ptr(), chan.data_ptr(),
+                                                0 if bec else 1, dec.data_ptr(), its.data_ptr(), B, mc.max_iters,
+                                                mc.expurgation, int(stop_frame_errors), counters.data_ptr(),
+                                                s.cuda_stream)
+        _native.check(rc, "ldpc_mc_rm_count_dev")
+    return run
+
+
 CODEWORDS = ("zero", "random")
 
 
@@ -179,12 +247,19 @@ class MonteCarlo:
     the all-zero one, and errors are counted against it -- the validation mode for decoders with ties
     (a zero posterior decides 0, which the all-zero shortcut counts as correct).  Fixed codes on the
     BSC and BI-AWGN, every decoder above; unfused, so of the curve only the two ends (channel and
-    final errors) are counted."""
+    final errors) are counted.
+    rate_match=ratematch.RateMatch(...): the code as its standard sends it (rate_match_executor) --
+    punctured positions reach the decoder as erasures / LLRs of +0, shortened ones as known zeros
+    (+known_llr), and errors are counted over the description's count mask (ber is per counted bit).
+    Fixed codes; every channel (the BEC with the all-zero codeword), every decoder above --
+    algo="gallager" only without punctured positions: a hard-decision decoder has no received bit
+    there -- and both codewords= modes; codewords="random" needs every shortened position to be an
+    information position of the encoder.  Unfused like codewords="random"."""
 
     def __init__(self, graph, channel, param, max_iters, algo="spa", alpha=1.0, early_stop=True,
                  expurgation=-1, seed=0, batch=4096, process_group=None, executor=None, device=None,
                  optimal=False, message_passing=True, schedule="flooding", quant=None, flip_threshold=0,
-                 codewords="zero"):
+                 codewords="zero", rate_match=None, known_llr=1024.0):
         import torch
         self.torch = torch
         self.graph = graph
@@ -202,6 +277,20 @@ class MonteCarlo:
             if self.channel == CHANNELS["bec"]:
                 raise ValueError('codewords="random" is for the BSC and BI-AWGN: erasure decoding does not depend '
                                  "on the codeword")
+        self.rate_match = rate_match
+        self.known_llr = float(known_llr)
+        if rate_match is not None:
+            if isinstance(graph, _Ensemble):
+                raise ValueError("rate_match= needs a fixed code: a description names the variables of one graph")
+            if optimal:
+                raise ValueError("rate_match= has no ML mode")
+            if rate_match.n != graph.n:
+                raise ValueError(f"the rate-matching description is of n = {rate_match.n}, the graph of n = {graph.n}")
+            if self.gallager and rate_match.n_punct:
+                raise ValueError('algo="gallager" cannot decode punctured positions: a hard-decision decoder has no '
+                                 "received bit there (known positions are fine)")
+            if not (np.isfinite(self.known_llr) and self.known_llr > 0):
+                raise ValueError("known_llr must be finite and > 0")
         if self.gallager:
             if self.channel != CHANNELS["bsc"]:
                 raise ValueError('algo="gallager" decodes the BSC only')
@@ -244,6 +333,8 @@ class MonteCarlo:
         if executor is None:
             if self.optimal:
                 executor = ml_executor(self)
+            elif self.rate_match is not None:
+                executor = rate_match_executor(self)
             elif self.codewords == "random":
                 executor = codeword_executor(self)
             elif self.gallager:
@@ -403,9 +494,13 @@ class MonteCarlo:
                 return out
         trials = int(g[0])
         curve = g[_native.MC_NCOUNT:].astype(np.float64)
-        if self.codewords == "random":  # unfused: only the two ends of the curve are counted
+        if self.codewords == "random" or self.rate_match is not None:  # unfused: only the two ends of the curve
             curve[1:-1] = np.nan
-            out = {**out, "codewords": "random", "channel_bit_errors": int(g[_native.MC_NCOUNT])}
+            out = {**out, "codewords": self.codewords, "channel_bit_errors": int(g[_native.MC_NCOUNT])}
+        if self.rate_match is not None:  # rates per counted bit; curve[0] counts the transmitted ones among them only
+            rm = self.rate_match
+            n = int(rm.counts().sum())
+            out = {**out, "rate_match": {"n_tx": rm.n_tx, "n_punct": rm.n_punct, "n_known": rm.n_known, "n_count": n}}
         return {**out,
             "num_tests": trials,
             "frame_errors": int(g[1]),

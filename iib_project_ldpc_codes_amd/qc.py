@@ -90,6 +90,18 @@ class QCCode:
     def graph(self):
         return QCGraph(self)
 
+    def rate_match(self, punctured_cols=(), shortened_cols=(), count="codeword"):
+        """A ratematch.RateMatch of whole block columns: column c stands for its Z variables c Z ..
+        c Z + Z - 1 (5G NR never sends its first two block columns)."""
+        from .ratematch import RateMatch
+
+        def expand(what, cols):
+            cols = np.asarray(cols, dtype=np.int64).ravel()
+            if cols.size and (cols.min() < 0 or cols.max() >= self.nb):
+                raise ValueError(f"QCCode.rate_match: a {what} block column outside [0, {self.nb})")
+            return (cols[:, None] * self.Z + np.arange(self.Z)[None, :]).ravel()
+        return RateMatch(self.n, expand("punctured", punctured_cols), expand("shortened", shortened_cols), count)
+
 
 class QCGraph(TannerGraph):
     """The expansion of a QCCode: a CSR TannerGraph whose device handle is made by

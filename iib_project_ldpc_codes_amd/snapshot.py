@@ -73,6 +73,8 @@ def config(mc):
         cfg.update({"algo": "gallager", "flip_threshold": int(mc.flip_threshold)})
     if getattr(mc, "codewords", "zero") == "random":  # only then: all-zero snapshots stay as they always were
         cfg["codewords"] = "random"
+    if getattr(mc, "rate_match", None) is not None:  # only then, as above: the description's digest and the known LLR
+        cfg["rate_match"] = {"sha1": mc.rate_match.digest(), "known_llr": float(mc.known_llr)}
     return cfg
 
 

@@ -357,6 +357,84 @@ int ldpc_mc_cw_count_dev(const uint8_t *d_cw, const void *d_chan, int chan_is_ll
 int ldpc_debug_encode_plan(int count, const int32_t *calls, int64_t *out, char *names);
 
 /* ---------------------------------------------------------------------- */
+/* Rate matching: punctured and known (shortened) positions               */
+/* (csrc/rate_match_host.cpp, csrc/rate_match.hip)                         */
+/* ---------------------------------------------------------------------- */
+/*
+ * The standards' quasi-cyclic codes do not transmit every variable.  A rate-matching
+ * description of a length-n code has two parts.
+ *
+ * The class cls[v] of each variable:
+ *   LDPC_RM_TX    transmitted;
+ *   LDPC_RM_PUNCT not transmitted, the receiver knows nothing;
+ *   LDPC_RM_KNOWN not transmitted, the receiver knows the bit (a shortened position
+ *                 is a known position whose bit is 0).
+ * The count mask count[v] in {0, 1}: its default (count = NULL) is 1 exactly where
+ * cls[v] != LDPC_RM_KNOWN -- a punctured bit is part of the codeword and must be
+ * recovered, a known bit is not counted.
+ *
+ * On the device the description is one byte per variable, bits 0-1 the class, bit 2
+ * the count, padded to a multiple of four bytes; a padding byte is LDPC_RM_PUNCT,
+ * uncounted (the value 1).  ldpc_debug_rate_match_pack writes these bytes and info =
+ * {n, n_tx, n_punct, n_known, n_count} on the host alone (no device; packed and info
+ * may each be NULL).  ldpc_rate_match_create validates on the host and uploads once
+ * to the current device.
+ *
+ * ldpc_channel_rm_dev: the output for trial t = first_cw + row, codeword bit x (bit 0
+ * of d_cw's byte; d_cw NULL: x = 0 everywhere), position v (d_out uint8[B*n] on the
+ * BEC, float[B*n] on the BSC and BI-AWGN):
+ *   LDPC_RM_TX:    ldpc_channel_cw_dev's value, bit for bit (one copy of the
+ *                  arithmetic serves both).  The Philox stream is indexed by position,
+ *                  so puncturing a position changes nothing at any other position.
+ *   LDPC_RM_PUNCT: BEC: 2.  BSC / AWGN: +0.0f (the sign bit is clear).
+ *   LDPC_RM_KNOWN: BEC: x, never erased.  BSC / AWGN: x ? -known_llr : +known_llr.
+ * known_llr must be finite and > 0.  1024 saturates every decoder of this library:
+ * the fp32 kernels clamp internally, the quantiser saturates to Q at any scale >= 1/16.
+ * Four positions none of which is transmitted cost no Philox block and no Box-Muller
+ * pair, only their stores.
+ *
+ * ldpc_mc_rm_count_dev: per trial a row of max_iters + 1 entries, as
+ * ldpc_mc_cw_count_dev's, its interior zero:
+ *   row[0]         = channel errors over the positions with class LDPC_RM_TX and
+ *                    count = 1: chan_kind 1 (d_chan float[B*n]): [llr < 0] != x;
+ *                    chan_kind 2 (d_chan uint8[B*n] of received bits): bit 0 != x;
+ *                    chan_kind 0 (d_chan uint8[B*n] of BEC words): word == 2;
+ *   row[max_iters] = final errors over the positions with count = 1: d_dec's bit 0 !=
+ *                    x, or with chan_kind 0 (d_dec uint8[B*n] of decoded BEC words)
+ *                    word == 2.
+ * The rows then take ldpc_mc_cw_count_dev's reduction: the counter layout of
+ * ldpc_mc_batch_dev, its expurgation and its sequential stop rule, on the final
+ * errors.  d_cw NULL: the all-zero codeword.  d_its may be NULL.
+ *
+ * The rate of the rate-matched code is R = (K - n_known) / n_tx, K the dimension of
+ * the mother code.
+ *
+ * Errors (LDPC_EINVAL): n < 1, a class byte above 2, a count byte above 1, a NULL
+ * handle, B < 0 or max_iters < 0, a chan_kind outside 0..2, a bad channel parameter or
+ * known_llr, a NULL buffer that would be read or written with B > 0.  B = 0 is a
+ * no-op.  Both device entries are asynchronous on `stream` and take the workspace and
+ * its lock as ldpc_channel_cw_dev and ldpc_mc_cw_count_dev do.
+ */
+#define LDPC_RM_TX 0
+#define LDPC_RM_PUNCT 1
+#define LDPC_RM_KNOWN 2
+typedef struct ldpc_rate_match ldpc_rate_match;
+int ldpc_rate_match_create(int n, const uint8_t *cls /* host [n] */, const uint8_t *count /* host [n], NULL = default */,
+                           ldpc_rate_match **out);
+void ldpc_rate_match_destroy(ldpc_rate_match *rm);
+int ldpc_rate_match_info(const ldpc_rate_match *rm, int32_t *n, int32_t *n_tx, int32_t *n_punct, int32_t *n_known,
+                         int32_t *n_count);
+int ldpc_channel_rm_dev(const ldpc_rate_match *rm, int channel, float param, float known_llr, uint64_t seed,
+                        uint64_t first_cw, int B, const uint8_t *d_cw /* NULL = all-zero */, void *d_out, void *stream);
+int ldpc_mc_rm_count_dev(const ldpc_rate_match *rm, const uint8_t *d_cw /* NULL = all-zero */, const void *d_chan,
+                         int chan_kind /* 0 BEC words, 1 float LLRs, 2 received bits */,
+                         const uint8_t *d_dec /* hard bits, or BEC words when chan_kind = 0 */,
+                         const int32_t *d_its /* may be NULL */, int B, int max_iters, int expurgation,
+                         int64_t stop_frame_errors, int64_t *d_counters, void *stream);
+int ldpc_debug_rate_match_pack(int n, const uint8_t *cls, const uint8_t *count, uint8_t *packed /* [4*ceil(n/4)] */,
+                               int32_t *info /* [5] */);
+
+/* ---------------------------------------------------------------------- */
 /* Layered (row-serial) schedule on a fixed code (csrc/bp_layer.hip)       */
 /* ---------------------------------------------------------------------- */
 /*

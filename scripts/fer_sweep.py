@@ -19,6 +19,11 @@ code and crossover points (decoder.gallager_decode_dev), to set beside min-sum.
 --codewords random (cfg3, cfg4): every trial transmits a random codeword and errors are counted
 against it (MonteCarlo codewords="random": encode, codeword channel, decode, count; unfused) -- no
 all-zero shortcut, so a decoder's ties are not counted as correct.
+--puncture / --shorten LIST (cfg3, cfg4, qc) and --puncture-cols / --shorten-cols LIST (qc: whole block
+columns): rate matching (MonteCarlo rate_match=, ratematch.RateMatch) -- the listed variables are not
+transmitted; a punctured one reaches the decoder as an LLR of +0, a shortened one as a known 0.  LIST:
+comma-separated indices and ranges a-b, or @FILE holding them.  Errors are counted over the positions
+that are not known, `rate` and `ebn0_db` are the rate-matched code's (K - n_known) / n_tx.
 One process per GPU: `--gpus N` starts the N ranks itself (decided before any HIP call, refused
 when fewer than N GPUs are visible -- iib_project_ldpc_codes_amd/launch.py, the same plan as
 bench.py), or runs as a rank of an external torchrun; trials shard by index, counters are
@@ -34,6 +39,8 @@ parallel_simulator.py:198), --trials, or --seconds.
   python scripts/fer_sweep.py cfg3 --schedule layered --quant 5,7,2.0,8,1 --codewords random --points 0.06
   python scripts/fer_sweep.py qc --array 3,6,1667 --schedule layered --quant 6,8,2.0,6,0 --points 0.05
   python scripts/fer_sweep.py qc --base table.txt --Z 81 --schedule layered --points 0.04
+  python scripts/fer_sweep.py qc --base table.txt --Z 81 --puncture-cols 0,1 --shorten @fill.txt --codewords random \
+      --schedule layered --quant 6,8,2.0,6,0 --points 0.04
 """
 import argparse
 import json
@@ -62,6 +69,21 @@ def parse_quant(text):
         return Quant(int(f[0]), int(f[1]), float(f[2]), int(f[3]), int(f[4]))
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
+
+
+def parse_indices(text):
+    """"3,7,10-12" or @FILE (the same, whitespace or commas between entries) -> [3, 7, 10, 11, 12]"""
+    if text.startswith("@"):
+        with open(text[1:]) as f:
+            text = f.read()
+    out = []
+    try:
+        for tok in text.replace(",", " ").split():
+            a, _, b = tok.partition("-")
+            out.extend(range(int(a), int(b) + 1) if b else [int(a)])
+    except ValueError:
+        raise argparse.ArgumentTypeError("an index list is comma-separated integers and ranges a-b, or @FILE")
+    return out
 
 
 def parse(argv=None):
@@ -93,6 +115,13 @@ def parse(argv=None):
     ap.add_argument("--codewords", choices=["zero", "random"], default="zero",
                     help="cfg3 / cfg4: random transmits a random codeword per trial and counts against it "
                          "(MonteCarlo codewords=, the unfused validation mode)")
+    ap.add_argument("--puncture", type=parse_indices, default=[], metavar="LIST",
+                    help="cfg3 / cfg4 / qc: variables that are not transmitted (indices, ranges a-b, or @FILE)")
+    ap.add_argument("--shorten", type=parse_indices, default=[], metavar="LIST",
+                    help="cfg3 / cfg4 / qc: variables that are known zeros and not transmitted")
+    ap.add_argument("--puncture-cols", type=parse_indices, default=[], metavar="LIST", help="qc: punctured block columns")
+    ap.add_argument("--shorten-cols", type=parse_indices, default=[], metavar="LIST", help="qc: shortened block columns")
+    ap.add_argument("--known-llr", type=float, default=1024.0, help="the LLR magnitude of a shortened position")
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks, one process per GPU (default: torchrun's WORLD_SIZE, else 1); "
                          "without WORLD_SIZE the sweep starts them itself")
@@ -120,7 +149,24 @@ def parse(argv=None):
         ap.error("--flip-threshold belongs to --algo gallager")
     if args.codewords == "random" and args.config == "ens":
         ap.error("--codewords random needs a fixed code (cfg3, cfg4): a per-trial graph has no encoder")
+    if (args.puncture_cols or args.shorten_cols) and args.config != "qc":
+        ap.error("--puncture-cols and --shorten-cols belong to qc (block columns)")
+    if (args.puncture or args.shorten) and args.config == "ens":
+        ap.error("--puncture and --shorten need a fixed code: a description names the variables of one graph")
     return args
+
+
+def rate_match_of(args, g):
+    """The ratematch.RateMatch of the command line, or None when it names no position."""
+    if not (args.puncture or args.shorten or args.puncture_cols or args.shorten_cols):
+        return None
+    from iib_project_ldpc_codes_amd.ratematch import RateMatch
+    punct, short = list(args.puncture), list(args.shorten)
+    if args.config == "qc":
+        cols = g.code.rate_match(args.puncture_cols, args.shorten_cols)
+        punct += [int(v) for v in cols.punctured]
+        short += [int(v) for v in cols.shortened]
+    return RateMatch(g.n, punct, short)
 
 
 def main(argv=None):
@@ -171,6 +217,7 @@ def main(argv=None):
         points = [float(p) for p in (args.points or "0.86,0.84,0.82,0.80,0.78").split(",")]
         batch = args.batch or 16384
     n, rate = (64800, 0.5) if g is None else (g.n, 1.0 - g.m / g.n)
+    rm = None if g is None else rate_match_of(args, g)
     for p in points:
         if g is None:
             mc = MonteCarlo.ensemble(n, 3, 6, channel, p, iters, algo=algo, alpha=alpha, early_stop=True,
@@ -178,7 +225,10 @@ def main(argv=None):
         else:
             mc = MonteCarlo(g, channel, p, iters, algo=algo, alpha=alpha, early_stop=True, seed=args.seed,
                             batch=batch, schedule=args.schedule, quant=args.quant, flip_threshold=args.flip_threshold,
-                            codewords=args.codewords)
+                            codewords=args.codewords, rate_match=rm, known_llr=args.known_llr)
+            if rm is not None:  # the rate-matched code's rate, from the encoder's dimension where the run has one
+                K = mc.encoder.K if hasattr(mc, "encoder") else g.n - g.m
+                rate = rm.rate(K)
         ck = None
         if args.checkpoint_dir:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
@@ -193,6 +243,8 @@ def main(argv=None):
                 tag += "_gallager-b%d" % args.flip_threshold
             if args.codewords == "random":
                 tag += "_cw-random"
+            if rm is not None:
+                tag += "_rm-" + rm.digest()[:12]
             ck = os.path.join(args.checkpoint_dir, f"{args.config}{tag}_p={p}_seed={args.seed}_B={batch}.json")
             if os.path.exists(ck):
                 mc.restore(snapshot.load(ck))
@@ -218,6 +270,8 @@ def main(argv=None):
                 out["flip_threshold"] = args.flip_threshold
             if args.codewords == "random":
                 out["codewords"] = "random"
+            if rm is not None:
+                out["rate_match"] = dict(res["rate_match"], sha1=rm.digest(), known_llr=args.known_llr)
             if channel == "awgn":
                 out["ebn0_db"] = float(de.sigma_to_ebn0_db(p, rate))
             print(json.dumps(out), flush=True)
