@@ -82,6 +82,9 @@ SIGNATURES = {
     "ldpc_bp_layered_q_decode_batch_dev": ([P, P, i, i, P, i, P, P, P, P], i),
     "ldpc_mc_layered_q_batch_dev": ([P, i, f, u64, u64, i, i, P, i, i, i64, P, P], i),
     "ldpc_debug_layer_q_plan": ([P, P, P, P, i, i, i, P, i, P, P], i),
+    "ldpc_mc_layered_q_cw_batch_dev": ([P, P, P, i, f, f, u64, u64, i, i, P, i, i, i64, P, P], i),
+    "ldpc_debug_layer_q_cw_plan": ([P, P, P, P, i, i, i, P, i, i, P, P], i),
+    "ldpc_debug_qc_cw_plan": ([i, i, i, P, i, P, i, i, P, P], i),
     "ldpc_quant_check": ([P], i),
     "ldpc_graph_create_qc": ([i, i, i, P, ct.POINTER(P)], i),
     "ldpc_graph_layer_rule": ([P], ct.c_char_p),

@@ -67,12 +67,20 @@ hipError_t LayerQFamily::launch(const BpPlan &p, const SoftCall &c, float *, hip
     a.Pmax = (1 << (q.post_bits - 1)) - 1;
     a.norm8 = q.norm8;
     a.offset = q.offset;
+    CwArgs cw{};
+    if (c.cw_mode) {
+        cw.desc = reinterpret_cast<const uint32_t *>(c.rm);
+        cw.cw = c.cw;
+        cw.known = c.known_llr;
+        cw.vec = g.n % 4 == 0 && (reinterpret_cast<uintptr_t>(c.cw) & 3) == 0;
+    }
+    const CwArgs *cwp = c.cw_mode ? &cw : nullptr;
     if (p.path >= BpPath::QcQ64x8) {  // a quasi-cyclic graph on its row table
         if (!g.qc_row || g.qc_Z <= 0 || g.lay_L != g.qc_mb) return hipErrorNotSupported;
         a.L = g.qc_mb;
-        return launch_qc_q(p, QcQArgs{a, g.qc_row, g.qc_Z}, c.early_stop, c.mc, s);
+        return launch_qc_q(p, QcQArgs{a, g.qc_row, g.qc_Z}, c.early_stop, c.mc, cwp, s);
     }
-    return launch_layer_q(p, a, c.early_stop, c.mc, s);
+    return launch_layer_q(p, a, c.early_stop, c.mc, cwp, s);
 }
 
 }  // namespace ldpc

@@ -15,8 +15,13 @@
 namespace ldpc {
 namespace {
 
-template <int T, int MAXDC, bool ET, bool MC>
-__global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a) {
+// Cw: nothing, or one CwArgs behind the plain arguments -- the codeword mode (only with MC):
+// cw_stage in place of the fused channel, cw_count in place of the count of negative bytes, the bit
+// plane after the records (bp_layer_q.hpp); the loop is the same.
+template <int T, int MAXDC, bool ET, bool MC, typename... Cw>
+__global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a, Cw... cwa) {
+    constexpr bool CW = sizeof...(Cw) > 0;
+    static_assert(MC || !CW, "the codeword mode is a Monte-Carlo mode");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int RW = MAXDC <= 16 ? 1 : 2;  // words of a record
     const int tid = threadIdx.x;
@@ -62,16 +67,20 @@ __global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a) {
         if (MC) {
             for (int i = tid; i <= iters; i += T) curve[i] = 0;
         }
-        for (int v = n + tid; v < 4 * n4; v += T) P[v] = 0;  // the padding bytes
         int err0 = 0;
-        for (int v = tid; v < n; v += T) {
-            const float l = MC ? chan_soft(a.ch, cw, v) : a.llr[(size_t)b * n + v];
-            const int c = quantise(l, a.scale, Q);
-            P[v] = (signed char)c;
-            err0 += (c < 0);
-            if (!MC && iters == 0) {  // no iteration: the quantised channel values themselves
-                if (a.post) a.post[(size_t)b * n + v] = (int8_t)c;
-                if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(c < 0);
+        if constexpr (CW) {
+            err0 = cw_stage<T>(a, cw_args(cwa...), b, cw, Pw, rec + m * RW);
+        } else {
+            for (int v = n + tid; v < 4 * n4; v += T) P[v] = 0;  // the padding bytes
+            for (int v = tid; v < n; v += T) {
+                const float l = MC ? chan_soft(a.ch, cw, v) : a.llr[(size_t)b * n + v];
+                const int c = quantise(l, a.scale, Q);
+                P[v] = (signed char)c;
+                err0 += (c < 0);
+                if (!MC && iters == 0) {  // no iteration: the quantised channel values themselves
+                    if (a.post) a.post[(size_t)b * n + v] = (int8_t)c;
+                    if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(c < 0);
+                }
             }
         }
         for (int i = tid; i < m * RW; i += T) rec[i] = 0;  // R = 0
@@ -101,7 +110,11 @@ __global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a) {
             ++it;
             if (MC) {
                 int errs = 0;
-                for (int w = tid; w < n4; w += T) errs += neg_bytes(w);
+                if constexpr (CW) {  // against the codeword's plane, under the description's count mask
+                    errs = cw_count<T>(Pw, rec + m * RW, cw_args(cwa...).desc, n4);
+                } else {
+                    for (int w = tid; w < n4; w += T) errs += neg_bytes(w);
+                }
                 count(it, errs);
             }
             if constexpr (ET) {
@@ -143,9 +156,16 @@ __global__ __launch_bounds__(T) void bp_layer_q_kernel(LayerQArgs a) {
 }
 
 template <int MAXDC>
-hipError_t launch_layer_q_shape(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s) {
+hipError_t launch_layer_q_shape(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, const CwArgs *cw,
+                                hipStream_t s) {
     constexpr int T = 256;
     if (p.threads != T) return hipErrorInvalidValue;
+    if (cw) {  // the codeword mode: Monte-Carlo only
+        if (!mc) return hipErrorInvalidValue;
+        auto go = [&](auto k) { return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a, *cw); };
+        return et ? go(bp_layer_q_kernel<T, MAXDC, true, true, CwArgs>)
+                  : go(bp_layer_q_kernel<T, MAXDC, false, true, CwArgs>);
+    }
     auto go = [&](auto k) { return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a); };
     if (et) return mc ? go(bp_layer_q_kernel<T, MAXDC, true, true>) : go(bp_layer_q_kernel<T, MAXDC, true, false>);
     return mc ? go(bp_layer_q_kernel<T, MAXDC, false, true>) : go(bp_layer_q_kernel<T, MAXDC, false, false>);
@@ -153,11 +173,11 @@ hipError_t launch_layer_q_shape(const BpPlan &p, const LayerQArgs &a, bool et, b
 
 }  // namespace
 
-hipError_t launch_layer_q(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s) {
+hipError_t launch_layer_q(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, const CwArgs *cw, hipStream_t s) {
     switch (p.path) {
-        case BpPath::LayerQ8: return launch_layer_q_shape<8>(p, a, et, mc, s);
-        case BpPath::LayerQ16: return launch_layer_q_shape<16>(p, a, et, mc, s);
-        case BpPath::LayerQ32: return launch_layer_q_shape<32>(p, a, et, mc, s);
+        case BpPath::LayerQ8: return launch_layer_q_shape<8>(p, a, et, mc, cw, s);
+        case BpPath::LayerQ16: return launch_layer_q_shape<16>(p, a, et, mc, cw, s);
+        case BpPath::LayerQ32: return launch_layer_q_shape<32>(p, a, et, mc, cw, s);
         default: return hipErrorNotSupported;
     }
 }

@@ -263,10 +263,15 @@ BpPlan bp_layer_plan(const GraphShape &g, int B, int iters, int /*algo*/, bool /
 // there is no kernel.  algo (min-sum only), early stop and want_post do not enter the layout.
 BpPlan bp_layer_q_plan(const GraphShape &g, int B, int iters, int /*algo*/, bool /*early_stop*/, bool mc,
                        bool /*want_post*/, int /*cus*/) {
+    return bp_layer_q_cw_plan(g, B, iters, mc, false);
+}
+
+BpPlan bp_layer_q_cw_plan(const GraphShape &g, int B, int iters, bool mc, bool cw) {
     BpPlan p;
     if (!g.consistent || g.lay_L <= 0 || g.max_cdeg > kLayerMaxD) return p;
+    if (cw && !mc) return p;  // the codeword mode is a Monte-Carlo mode
     const size_t lds = (mc ? curve_bytes(iters) : 0) + (((size_t)g.n + 3) & ~(size_t)3) +
-                       layer_q_record_bytes(g.max_cdeg) * (size_t)g.m;
+                       layer_q_record_bytes(g.max_cdeg) * (size_t)g.m + (cw ? layer_q_plane_bytes(g.n) : 0);
     if (lds > kLdsMax - 4096) return p;  // gmem_plan's budget; no slab form
     if (g.qc_Z > 0) {
         // a quasi-cyclic graph: bp_qc_q_kernel, one wave when a block row has no more checks

@@ -18,8 +18,12 @@
 namespace ldpc {
 namespace {
 
-template <int T, int MAXDC, bool ET, bool MC>
-__global__ __launch_bounds__(T) void bp_qc_q_kernel(QcQArgs qa) {
+// Cw: nothing, or one CwArgs behind the plain arguments -- the codeword mode (only with MC), as in
+// bp_layer_q.hip: cw_stage, cw_count and the bit plane after the records (bp_layer_q.hpp).
+template <int T, int MAXDC, bool ET, bool MC, typename... Cw>
+__global__ __launch_bounds__(T) void bp_qc_q_kernel(QcQArgs qa, Cw... cwa) {
+    constexpr bool CW = sizeof...(Cw) > 0;
+    static_assert(MC || !CW, "the codeword mode is a Monte-Carlo mode");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int RW = MAXDC <= 16 ? 1 : 2;  // words of a record
     const LayerQArgs &a = qa.q;
@@ -59,16 +63,20 @@ __global__ __launch_bounds__(T) void bp_qc_q_kernel(QcQArgs qa) {
         if (MC) {
             for (int i = tid; i <= iters; i += T) curve[i] = 0;
         }
-        for (int v = n + tid; v < 4 * n4; v += T) P[v] = 0;  // the padding bytes
         int err0 = 0;
-        for (int v = tid; v < n; v += T) {
-            const float l = MC ? chan_soft(a.ch, cw, v) : a.llr[(size_t)b * n + v];
-            const int c = quantise(l, a.scale, Q);
-            P[v] = (signed char)c;
-            err0 += (c < 0);
-            if (!MC && iters == 0) {  // no iteration: the quantised channel values themselves
-                if (a.post) a.post[(size_t)b * n + v] = (int8_t)c;
-                if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(c < 0);
+        if constexpr (CW) {
+            err0 = cw_stage<T>(a, cw_args(cwa...), b, cw, Pw, rec + m * RW);
+        } else {
+            for (int v = n + tid; v < 4 * n4; v += T) P[v] = 0;  // the padding bytes
+            for (int v = tid; v < n; v += T) {
+                const float l = MC ? chan_soft(a.ch, cw, v) : a.llr[(size_t)b * n + v];
+                const int c = quantise(l, a.scale, Q);
+                P[v] = (signed char)c;
+                err0 += (c < 0);
+                if (!MC && iters == 0) {  // no iteration: the quantised channel values themselves
+                    if (a.post) a.post[(size_t)b * n + v] = (int8_t)c;
+                    if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(c < 0);
+                }
             }
         }
         for (int i = tid; i < m * RW; i += T) rec[i] = 0;  // R = 0
@@ -89,7 +97,11 @@ __global__ __launch_bounds__(T) void bp_qc_q_kernel(QcQArgs qa) {
             ++it;
             if (MC) {
                 int errs = 0;
-                for (int w = tid; w < n4; w += T) errs += neg_bytes(w);
+                if constexpr (CW) {  // against the codeword's plane, under the description's count mask
+                    errs = cw_count<T>(Pw, rec + m * RW, cw_args(cwa...).desc, n4);
+                } else {
+                    for (int w = tid; w < n4; w += T) errs += neg_bytes(w);
+                }
                 count(it, errs);
             }
             if constexpr (ET) {
@@ -130,8 +142,13 @@ __global__ __launch_bounds__(T) void bp_qc_q_kernel(QcQArgs qa) {
 }
 
 template <int T, int MAXDC>
-hipError_t launch_qc_q_shape(const BpPlan &p, const QcQArgs &a, bool et, bool mc, hipStream_t s) {
+hipError_t launch_qc_q_shape(const BpPlan &p, const QcQArgs &a, bool et, bool mc, const CwArgs *cw, hipStream_t s) {
     if (p.threads != T) return hipErrorInvalidValue;
+    if (cw) {  // the codeword mode: Monte-Carlo only
+        if (!mc) return hipErrorInvalidValue;
+        auto go = [&](auto k) { return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a, *cw); };
+        return et ? go(bp_qc_q_kernel<T, MAXDC, true, true, CwArgs>) : go(bp_qc_q_kernel<T, MAXDC, false, true, CwArgs>);
+    }
     auto go = [&](auto k) { return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a); };
     if (et) return mc ? go(bp_qc_q_kernel<T, MAXDC, true, true>) : go(bp_qc_q_kernel<T, MAXDC, true, false>);
     return mc ? go(bp_qc_q_kernel<T, MAXDC, false, true>) : go(bp_qc_q_kernel<T, MAXDC, false, false>);
@@ -139,10 +156,10 @@ hipError_t launch_qc_q_shape(const BpPlan &p, const QcQArgs &a, bool et, bool mc
 
 }  // namespace
 
-hipError_t launch_qc_q(const BpPlan &p, const QcQArgs &a, bool et, bool mc, hipStream_t s) {
+hipError_t launch_qc_q(const BpPlan &p, const QcQArgs &a, bool et, bool mc, const CwArgs *cw, hipStream_t s) {
     switch (p.path) {
 #define LDPC_ROW(T, D) \
-    case BpPath::QcQ##T##x##D: return launch_qc_q_shape<T, D>(p, a, et, mc, s);
+    case BpPath::QcQ##T##x##D: return launch_qc_q_shape<T, D>(p, a, et, mc, cw, s);
         LDPC_QC_Q_SHAPES(LDPC_ROW)
 #undef LDPC_ROW
         default: return hipErrorNotSupported;

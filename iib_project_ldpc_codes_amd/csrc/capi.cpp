@@ -89,9 +89,10 @@ static const char *const kNoSchedule =
 
 // The three plan entries of a fixed code: its host layouts, then write_plans' rows of `plan` (bp_plan,
 // bp_layer_plan or bp_layer_q_plan).  need_schedule: LDPC_EUNSUP up front for a graph without one.
+template <typename Plan>
 static int graph_plans(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
                        const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus, int64_t *out,
-                       char *names, decltype(bp_plan) *plan, bool need_schedule, int BpPlan::*col4) {
+                       char *names, Plan plan, bool need_schedule, int BpPlan::*col4, const char *no_plan = nullptr) {
     LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
     HostGraph h;
     LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
@@ -102,7 +103,7 @@ static int graph_plans(const int32_t *check_ptr, const int32_t *check_var, const
         set_error(kNoSchedule);
         return LDPC_EUNSUP;
     }
-    return write_plans(count, calls, out, names, col4, nullptr,
+    return write_plans(count, calls, out, names, col4, no_plan,
                        [&](int B, int iters, int algo, bool et, bool mc, bool want_post) {
                            return plan(g, B, iters, algo, et, mc, want_post, cus);
                        });
@@ -696,11 +697,12 @@ int ldpc_quant_check(const ldpc_quant *q) {
 
 // The checks the two fixed-point entries share; LDPC_EUNSUP for a graph without a schedule or
 // with a block beyond LDS
-static int layered_q_check(const ldpc_graph *g, const ldpc_quant *q, int B, int max_iters, bool mc) {
+static int layered_q_check(const ldpc_graph *g, const ldpc_quant *q, int B, int max_iters, bool mc, bool cw = false) {
     LDPC_TRY(ldpc_quant_check(q));
     LDPC_TRY(layered_check(g, LDPC_ALGO_MINSUM));
-    if (bp_layer_q_plan(*g, B, max_iters, 1, false, mc, false, 1).path == BpPath::None) {
-        set_error("the fixed-point layered block (posteriors and check records) does not fit LDS");
+    if (bp_layer_q_cw_plan(*g, B, max_iters, mc, cw).path == BpPath::None) {
+        set_error(cw ? "the fixed-point layered block (posteriors, check records and the codeword's bit plane) does not fit LDS"
+                         : "the fixed-point layered block (posteriors and check records) does not fit LDS");
         return LDPC_EUNSUP;
     }
     return LDPC_OK;
@@ -728,6 +730,40 @@ int ldpc_mc_layered_q_batch_dev(const ldpc_graph *g, int channel, float param, u
     const SoftCall c =
         mc_call(B, max_iters, LDPC_ALGO_MINSUM, 1.0f, early_stop, make_chan(channel, p, p2, seed), first_cw);
     return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream, soft_decode(LayerQFamily{*g, *q}));
+}
+
+static const char *const kNoCwPlan =
+    "no plan in the codeword mode: not a Monte-Carlo call, or the block with the codeword's bit plane does not fit LDS";
+
+int ldpc_mc_layered_q_cw_batch_dev(const ldpc_graph *g, const ldpc_rate_match *rm, const uint8_t *d_cw, int channel,
+                                   float param, float known_llr, uint64_t seed, uint64_t first_cw, int B,
+                                   int max_iters, const ldpc_quant *q, int early_stop, int expurgation,
+                                   int64_t stop_frame_errors, int64_t *d_counters, void *stream) {
+    LDPC_REQUIRE(g && d_counters && B >= 0 && max_iters >= 0, "bad MC arguments");
+    LDPC_REQUIRE(channel != LDPC_CH_BEC, "the layered schedule decodes the BSC and the BI-AWGN channel (BEC: ldpc_mc_batch_dev)");
+    float p, p2;
+    LDPC_TRY(channel_params(channel, param, &p, &p2));
+    LDPC_TRY(layered_q_check(g, q, B, max_iters, true, true));
+    if (rm) {
+        LDPC_REQUIRE(rm->n == g->n, "the rate-matching description is of another n than the graph");
+        LDPC_REQUIRE(rm->n_known == 0 || (std::isfinite(known_llr) && known_llr > 0.0f),
+                     "known_llr must be finite and > 0");
+    }
+    if (B == 0) return LDPC_OK;
+    SoftCall c = mc_call(B, max_iters, LDPC_ALGO_MINSUM, 1.0f, early_stop, make_chan(channel, p, p2, seed), first_cw);
+    c.cw_mode = true, c.cw = d_cw, c.rm = rm ? rm->desc : nullptr, c.known_llr = known_llr;
+    return mc_entry(c, expurgation, stop_frame_errors, d_counters, stream, soft_decode(LayerQFamily{*g, *q}));
+}
+
+int ldpc_debug_layer_q_cw_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                               const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
+                               int has_desc, int64_t *out, char *names) {
+    (void)has_desc;  // the count mask is re-read from the description: no LDS of its own
+    return graph_plans(check_ptr, check_var, var_ptr, var_slot, n, m, count, calls, cus, out, names,
+                       [](const GraphShape &g, int B, int iters, int, bool, bool mc, bool, int) {
+                           return bp_layer_q_cw_plan(g, B, iters, mc, true);
+                       },
+                       true, &BpPlan::wg_per_cu, kNoCwPlan);
 }
 
 int ldpc_debug_layer_q_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
@@ -760,8 +796,9 @@ int ldpc_debug_qc_expand(int mb, int nb, int Z, const int32_t *base, int32_t *ch
     return LDPC_OK;
 }
 
-int ldpc_debug_qc_plan(int mb, int nb, int Z, const int32_t *base, int count, const int32_t *calls, int cus,
-                       int64_t *out, char *names) {
+// cw: bp_layer_q_cw_plan's (false: ldpc_debug_qc_plan)
+static int qc_plans(int mb, int nb, int Z, const int32_t *base, int count, const int32_t *calls, int cus, bool cw,
+                    int64_t *out, char *names) {
     LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
     HostGraph h;
     QcCode qc;
@@ -775,10 +812,22 @@ int ldpc_debug_qc_plan(int mb, int nb, int Z, const int32_t *base, int count, co
         set_error(kNoSchedule);
         return LDPC_EUNSUP;
     }
-    return write_plans(count, calls, out, names, &BpPlan::wg_per_cu, nullptr,
+    return write_plans(count, calls, out, names, &BpPlan::wg_per_cu, cw ? kNoCwPlan : nullptr,
                        [&](int B, int iters, int algo, bool et, bool mc, bool want_post) {
+                           if (cw) return bp_layer_q_cw_plan(g, B, iters, mc, true);
                            return bp_layer_q_plan(g, B, iters, algo, et, mc, want_post, cus);
                        });
+}
+
+int ldpc_debug_qc_plan(int mb, int nb, int Z, const int32_t *base, int count, const int32_t *calls, int cus,
+                       int64_t *out, char *names) {
+    return qc_plans(mb, nb, Z, base, count, calls, cus, false, out, names);
+}
+
+int ldpc_debug_qc_cw_plan(int mb, int nb, int Z, const int32_t *base, int count, const int32_t *calls, int cus,
+                          int has_desc, int64_t *out, char *names) {
+    (void)has_desc;  // as ldpc_debug_layer_q_cw_plan
+    return qc_plans(mb, nb, Z, base, count, calls, cus, true, out, names);
 }
 
 // --------------------------- random graphs / ensemble MC -------------------

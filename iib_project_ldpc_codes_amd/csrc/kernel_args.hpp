@@ -109,6 +109,15 @@ struct QcQArgs {
     int Z;
 };
 
+// The codeword mode of the two fixed-point kernels (ldpc_mc_layered_q_cw_batch_dev): one more
+// kernel argument behind the plain ones, which keep their layout
+struct CwArgs {
+    const uint32_t *desc;  // the rate-matching description, a dword per four positions; nullptr: all transmitted and counted
+    const uint8_t *cw;     // [B][n] codewords, bit 0; nullptr: all-zero
+    float known;           // |LLR| of a LDPC_RM_KNOWN position
+    int vec;               // n % 4 == 0 and cw 4-byte aligned: the four codeword bytes of a group in one load
+};
+
 // gb_kernel (gb.hip): Gallager A/B on bit planes
 struct GbArgs {
     const int32_t *cptr, *cvar, *vptr, *vslot;
@@ -151,10 +160,11 @@ hipError_t launch_irr(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, 
 hipError_t launch_generic(const BpPlan &p, const ldpc_graph &g, BpArgs a, int algo, bool et, bool mc, hipStream_t s);
 // bp_layer_kernel (bp_layer.hip), from a bp_layer_plan
 hipError_t launch_layer(const BpPlan &p, LayerArgs a, int algo, bool et, bool mc, hipStream_t s);
-// bp_layer_q_kernel (bp_layer_q.hip), from a bp_layer_q_plan
-hipError_t launch_layer_q(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, hipStream_t s);
-// bp_qc_q_kernel (bp_qc_q.hip), from a bp_layer_q_plan of a quasi-cyclic graph
-hipError_t launch_qc_q(const BpPlan &p, const QcQArgs &a, bool et, bool mc, hipStream_t s);
+// bp_layer_q_kernel (bp_layer_q.hip), from a bp_layer_q_plan; cw: the codeword mode
+// (the instantiation with a CwArgs, Monte-Carlo only), from a plan with its planes
+hipError_t launch_layer_q(const BpPlan &p, const LayerQArgs &a, bool et, bool mc, const CwArgs *cw, hipStream_t s);
+// bp_qc_q_kernel (bp_qc_q.hip), from a bp_layer_q_plan of a quasi-cyclic graph; cw as above
+hipError_t launch_qc_q(const BpPlan &p, const QcQArgs &a, bool et, bool mc, const CwArgs *cw, hipStream_t s);
 // Ensemble BEC Monte-Carlo by frontier peeling (peel.hip): launch_mc_bec_ensemble's BecKernel::Peel
 // plans; trial b decodes on the (dv, dc) regular graph b of the two lists.
 hipError_t launch_mc_bec_peel(const BecPlan &plan, int n, int m, int dv, int dc, const int32_t *check_lookup,

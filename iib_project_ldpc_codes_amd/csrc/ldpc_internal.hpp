@@ -319,6 +319,12 @@ BpPlan bp_layer_plan(const GraphShape &g, int B, int iters, int algo, bool early
 // LDS formula and cap: T = 64 (one wave) when Z <= 64, else 256; MAXDC by the largest block-row degree.
 BpPlan bp_layer_q_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post,
                        int cus);
+// The same in the codeword mode (cw; Monte-Carlo only: no plan otherwise): after the records the
+// block holds the codeword's bit plane of layer_q_plane_bytes(n).  A rate-matching description adds
+// nothing: its count mask is re-read from the description.  Names, threads, grid and the cap are
+// unchanged; wg_per_cu is that of the larger block.  cw = false is bp_layer_q_plan.
+BpPlan bp_layer_q_cw_plan(const GraphShape &g, int B, int iters, bool mc, bool cw);
+constexpr size_t layer_q_plane_bytes(size_t n) { return 4 * ((n + 31) / 32); }
 constexpr size_t layer_q_record_bytes(int max_cdeg) { return max_cdeg <= 16 ? 4 : 8; }
 constexpr size_t layer_block_bytes(size_t n, size_t E) { return pad16((n + E) * 4); }
 // Row l of lay_tab: [j] (j <= 32) = first word of the layer's j-th edges in lay_var (and in R): the
@@ -369,6 +375,11 @@ struct SoftCall {
     ChanArgs ch{};
     uint64_t first_cw = 0;
     int32_t *trial = nullptr;  // [B][max_iters+1] per-trial curves (then launch_mc_reduce)
+    // The codeword mode of the fixed-point family (mc only; ldpc_mc_layered_q_cw_batch_dev)
+    bool cw_mode = false;
+    const uint8_t *cw = nullptr;  // [B][n] codewords, bit 0; nullptr: all-zero
+    const uint8_t *rm = nullptr;  // the rate-matching description's packed bytes; nullptr: none
+    float known_llr = 0.0f;
 };
 
 // The soft-decoding families.  Each plans a call (its bp_*_plan, host only) and launches a plan
@@ -401,6 +412,7 @@ struct LayerQFamily {  // fixed-point layered min-sum (bp_layer_q.hip, bp_qc_q.h
     const ldpc_graph &g;
     const ldpc_quant &q;
     BpPlan plan(const SoftCall &c, int cus) const {
+        if (c.cw_mode) return bp_layer_q_cw_plan(g, c.B, c.max_iters, c.mc, true);
         return bp_layer_q_plan(g, c.B, c.max_iters, 1, c.early_stop, c.mc, c.post != nullptr, cus);
     }
     hipError_t launch(const BpPlan &p, const SoftCall &c, float *scratch, hipStream_t s) const;

@@ -177,6 +177,75 @@ def rate_match_executor(mc):
     return run
 
 
+def fused_codeword_executor(mc):
+    """Batch executor of fused=True: [information bits -> ratematch.shorten_info -> encode, with
+    codewords="random" only; otherwise no codeword is given and the entry means the all-zero one] ->
+    ldpc_mc_layered_q_cw_batch_dev, which draws the channel of the (rate-matched) codeword in the
+    fixed-point decoder's kernel and counts every iteration against the codeword under the count
+    mask.  Per batch size only the information and codeword buffers are kept."""
+    import ctypes as ct
+    from . import ratematch
+    from .encoder import Encoder
+    torch = mc.torch
+    rm = mc.rate_match
+    random = mc.codewords == "random"
+    enc = None
+    if random or (rm is not None and rm.count == "info"):
+        enc = getattr(mc.graph, "_encoder", None)  # one elimination per graph object, as codeword_executor
+        if enc is None:
+            enc = mc.graph._encoder = Encoder(mc.graph)
+        mc.encoder = enc
+        if rm is not None:
+            rm.bind(enc)
+    # a shortened parity position: ValueError here, not mid-run
+    short = ratematch.shortened_info_index(enc, rm) if random and rm is not None else np.zeros(0, np.int64)
+    n, K = mc.graph.n, (enc.K if random else 0)
+    bufs, short_dev = {}, {}
+
+    def run(first_cw, B, stop_frame_errors, counters, stream=None):
+        B = int(B)
+        if B <= 0:
+            return
+        s = stream if stream is not None else torch.cuda.current_stream()
+        cw = None
+        if random:
+            if B not in bufs:
+                u8 = dict(dtype=torch.uint8, device=counters.device)
+                bufs[B] = (torch.empty((B, K), **u8), torch.empty((B, n), **u8))
+            info, cw = bufs[B]
+            with torch.cuda.stream(s):
+                enc.info_bits_dev(mc.seed, first_cw, B, out=info, stream=s)
+                if short.size:
+                    if info.device not in short_dev:  # the index tensor: uploaded once per device
+                        short_dev[info.device] = torch.as_tensor(short, device=info.device)
+                    ratematch.shorten_info(info, enc, rm, index=short_dev[info.device])
+                enc.encode_dev(info, out=cw, stream=s)
+        q = mc.quant.native()
+        rc = _native.lib().ldpc_mc_layered_q_cw_batch_dev(
+            mc.graph.handle(), None if rm is None else rm.handle(), None if cw is None else cw.data_ptr(), mc.channel,
+            mc.param, mc.known_llr, mc.seed, int(first_cw), B, mc.max_iters, ct.addressof(q), int(mc.early_stop),
+            mc.expurgation, int(stop_frame_errors), counters.data_ptr(), s.cuda_stream)
+        _native.check(rc, "ldpc_mc_layered_q_cw_batch_dev")
+    return run
+
+
+def fused_check(fused, quant, schedule, channel, codewords, rate_match):
+    """ValueError unless fused=True is asked of a configuration that has the fused kernel: the
+    fixed-point layered decoder on the BSC or BI-AWGN, with random codewords or a rate-matching
+    description (or both)."""
+    if not fused:
+        return
+    if quant is None:
+        raise ValueError("fused=True needs quant=: the fused codeword mode is the fixed-point decoders'")
+    if schedule != "layered":
+        raise ValueError('fused=True needs schedule="layered"')
+    if channel not in ("bsc", "awgn"):
+        raise ValueError("fused=True is for the BSC and BI-AWGN")
+    if codewords != "random" and rate_match is None:
+        raise ValueError('fused=True needs codewords="random" or rate_match=: the all-zero, all-transmitted run '
+                         "is fused already")
+
+
 CODEWORDS = ("zero", "random")
 
 
@@ -254,12 +323,17 @@ class MonteCarlo:
     Fixed codes; every channel (the BEC with the all-zero codeword), every decoder above --
     algo="gallager" only without punctured positions: a hard-decision decoder has no received bit
     there -- and both codewords= modes; codewords="random" needs every shortened position to be an
-    information position of the encoder.  Unfused like codewords="random"."""
+    information position of the encoder.  Unfused like codewords="random".
+    fused=True: the two modes above on the fixed-point decoder in one kernel (fused_codeword_executor)
+    -- valid only with quant=, schedule="layered", the BSC or BI-AWGN and at least one of
+    codewords="random" / rate_match=.  The counts are the chain's on the same trials, and the curve
+    gains its interior: error_curve[t] is the error rate after iteration t over the counted positions
+    (error_curve[0] still over the transmitted ones among them)."""
 
     def __init__(self, graph, channel, param, max_iters, algo="spa", alpha=1.0, early_stop=True,
                  expurgation=-1, seed=0, batch=4096, process_group=None, executor=None, device=None,
                  optimal=False, message_passing=True, schedule="flooding", quant=None, flip_threshold=0,
-                 codewords="zero", rate_match=None, known_llr=1024.0):
+                 codewords="zero", rate_match=None, known_llr=1024.0, fused=False):
         import torch
         self.torch = torch
         self.graph = graph
@@ -269,6 +343,8 @@ class MonteCarlo:
         if codewords not in CODEWORDS:
             raise ValueError(f"codewords must be one of {CODEWORDS}, not {codewords!r}")
         self.codewords = codewords
+        self.fused = bool(fused)
+        fused_check(self.fused, None if self.gallager else quant, self.schedule, channel, codewords, rate_match)
         if codewords == "random":
             if isinstance(graph, _Ensemble):
                 raise ValueError('codewords="random" needs a fixed code: a per-trial graph has no encoder')
@@ -333,6 +409,8 @@ class MonteCarlo:
         if executor is None:
             if self.optimal:
                 executor = ml_executor(self)
+            elif self.fused:
+                executor = fused_codeword_executor(self)
             elif self.rate_match is not None:
                 executor = rate_match_executor(self)
             elif self.codewords == "random":
@@ -494,8 +572,9 @@ class MonteCarlo:
                 return out
         trials = int(g[0])
         curve = g[_native.MC_NCOUNT:].astype(np.float64)
-        if self.codewords == "random" or self.rate_match is not None:  # unfused: only the two ends of the curve
-            curve[1:-1] = np.nan
+        if self.codewords == "random" or self.rate_match is not None:
+            if not self.fused:  # unfused: only the two ends of the curve
+                curve[1:-1] = np.nan
             out = {**out, "codewords": self.codewords, "channel_bit_errors": int(g[_native.MC_NCOUNT])}
         if self.rate_match is not None:  # rates per counted bit; curve[0] counts the transmitted ones among them only
             rm = self.rate_match

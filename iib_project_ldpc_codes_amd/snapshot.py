@@ -75,6 +75,8 @@ def config(mc):
         cfg["codewords"] = "random"
     if getattr(mc, "rate_match", None) is not None:  # only then, as above: the description's digest and the known LLR
         cfg["rate_match"] = {"sha1": mc.rate_match.digest(), "known_llr": float(mc.known_llr)}
+    if getattr(mc, "fused", False):  # only then, as above: the fused run's curve has an interior, the chain's none
+        cfg["fused"] = True
     return cfg
 
 

@@ -521,6 +521,42 @@ int ldpc_bp_layered_q_decode_batch_dev(const ldpc_graph *g, const float *d_llr, 
 int ldpc_mc_layered_q_batch_dev(const ldpc_graph *g, int channel, float param, uint64_t seed, uint64_t first_cw,
                                 int B, int max_iters, const ldpc_quant *q, int early_stop, int expurgation,
                                 int64_t stop_frame_errors, int64_t *d_counters, void *stream);
+/*
+ * The fused Monte-Carlo batch above on a transmitted codeword and a rate-matched word: the
+ * channel is drawn in the decoder's kernel and every iteration is counted against the codeword
+ * under the count mask.  rm NULL: every position transmitted and counted; d_cw uint8[B][n], bit 0
+ * of each byte, NULL: the all-zero codeword.  For trial t = first_cw + row and position v, with
+ * codeword bit x_v:
+ *   channel  llr_v is exactly what ldpc_channel_rm_dev writes for (seed, t, v): the reflected stream
+ *            where the class is LDPC_RM_TX, +0.0f where LDPC_RM_PUNCT, x_v ? -known_llr : +known_llr
+ *            where LDPC_RM_KNOWN.  With rm NULL it is ldpc_channel_cw_dev's value, with d_cw NULL as
+ *            well ldpc_channel_dev's.  A group of four positions 4g .. 4g + 3 without a transmitted
+ *            one draws no Philox block.
+ *   decode   c_v = quantise(llr_v); then ldpc_bp_layered_q_decode_batch_dev's text, unchanged.  Early
+ *            stop tests the syndrome of the decisions (the transmitted word is a codeword).
+ *   row      max_iters + 1 entries per trial:
+ *              row[0] = #{v : class TX, count = 1, [llr_v < 0] != x_v}  (ldpc_mc_rm_count_dev's rule,
+ *                       on the sign of the float),
+ *              row[t] = #{v : count = 1, [P_v < 0] != x_v} after iteration t, repeated after a stop;
+ *            max_iters = 0: the one entry is the final count, of the quantised channel values
+ *            c_v.  its as in ldpc_mc_layered_q_batch_dev.
+ *   reduce   the rows go through ldpc_mc_batch_dev's reduction: counter layout, expurgation and
+ *            the sequential stop rule are its.
+ * So: counters [0..3], curve[0] and curve[max_iters] equal those of the unfused chain
+ * (ldpc_channel_rm_dev / ldpc_channel_cw_dev, ldpc_bp_layered_q_decode_batch_dev,
+ * ldpc_mc_rm_count_dev / ldpc_mc_cw_count_dev) on the same trials; the interior of the curve is what
+ * the chain cannot give.  With rm and d_cw both NULL everything except curve[0] equals
+ * ldpc_mc_layered_q_batch_dev's output: that entry counts c_v < 0 there and llr_v < 0 here, which
+ * differ wherever a small negative LLR quantises to 0.
+ * LDPC_EINVAL: LDPC_CH_BEC, a bad q or channel parameter, known_llr not finite and > 0 when rm has
+ * a LDPC_RM_KNOWN position, an rm of another n, NULL g / q / d_counters, B < 0 or max_iters < 0.
+ * LDPC_EUNSUP: a graph without a layer schedule, or whose block with the codeword's bit plane
+ * (ldpc_debug_layer_q_cw_plan) does not fit LDS.  B = 0 is a no-op.  Asynchronous on `stream`.
+ */
+int ldpc_mc_layered_q_cw_batch_dev(const ldpc_graph *g, const ldpc_rate_match *rm, const uint8_t *d_cw, int channel,
+                                   float param, float known_llr, uint64_t seed, uint64_t first_cw, int B,
+                                   int max_iters, const ldpc_quant *q, int early_stop, int expurgation,
+                                   int64_t stop_frame_errors, int64_t *d_counters, void *stream);
 
 /* ---------------------------------------------------------------------- */
 /* Whole Monte-Carlo run over several devices of one process */
@@ -801,6 +837,21 @@ int ldpc_debug_qc_expand(int mb, int nb, int Z, const int32_t *base, int32_t *ch
  */
 int ldpc_debug_qc_plan(int mb, int nb, int Z, const int32_t *base, int count, const int32_t *calls, int cus,
                        int64_t *out, char *names);
+/*
+ * Host-only: ldpc_debug_layer_q_plan and ldpc_debug_qc_plan in the codeword mode of
+ * ldpc_mc_layered_q_cw_batch_dev.  The block gains, after the records, one bit per variable for
+ * the codeword (4 ceil(n / 32) bytes); names, threads, grid and the cap are unchanged, and column 4
+ * is recomputed from the new LDS.  has_desc != 0: a rate-matching description is given -- it adds
+ * no LDS (the kernel re-reads the description for the count mask), so the rows are the same.  The
+ * mode exists for Monte-Carlo calls only: a row with mc = 0 is the row of no plan.  LDPC_EUNSUP,
+ * after every row is filled, when a row has no plan -- what ldpc_mc_layered_q_cw_batch_dev returns
+ * for that call.
+ */
+int ldpc_debug_layer_q_cw_plan(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                               const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
+                               int has_desc, int64_t *out, char *names);
+int ldpc_debug_qc_cw_plan(int mb, int nb, int Z, const int32_t *base, int count, const int32_t *calls, int cus,
+                          int has_desc, int64_t *out, char *names);
 
 /*
  * Host-only: the launch plans of `count` BEC erasure-decoding calls on a graph of n variables

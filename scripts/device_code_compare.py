@@ -7,7 +7,11 @@ Each csrc/*.hip file (default: every one that includes kernel_args.hpp) is compi
 assembly, device side only, with the Makefile's flags: once from REV (its csrc/ and include/ are
 extracted with `git archive` into a temporary directory) and once from the working tree.  The text
 is normalised, cut into kernels, and each kernel instantiation is reduced to an instruction count,
-a digest and its resources.  Needs hipcc and git, no GPU.  Exit status 1 when anything differs.
+a digest and its resources.  A kernel's own symbol is written <self> in its text, so an instantiation
+whose mangled name alone changed (a template parameter pack added behind the others, empty for it)
+compares equal under its demangled name.  An instantiation the parent does not have is listed as
+added ("identical": null) and is no difference.  Needs hipcc and git, no GPU.  Exit status 1 when
+anything differs.
 """
 import argparse
 import hashlib
@@ -26,7 +30,7 @@ CSRC = "iib_project_ldpc_codes_amd/csrc"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 HOW = ("hipcc --offload-arch=gfx950 --cuda-device-only -S with the Makefile's flags (" + " ".join(FLAGS) + ") on each "
        "file at each commit; .file / .ident lines, comments, the per-file __hip_cuid symbol and the function index "
-       "inside block labels (.LBB<i>_) normalised away; per kernel the function body up to .Lfunc_end: instructions "
+       "inside block labels (.LBB<i>_) normalised away, the kernel's own symbol written <self>; per kernel the function body up to .Lfunc_end: instructions "
        "counted, SHA-256 of the normalised text (first 16 hex digits), resources from its .amdhsa_kernel block "
        "(next_free_vgpr, next_free_sgpr, accum_offset, static LDS, scratch).  Made by scripts/device_code_compare.py.")
 RESOURCES = {"vgpr": "next_free_vgpr", "sgpr": "next_free_sgpr", "accum_offset": "accum_offset",
@@ -82,7 +86,7 @@ def kernels(text):
             sym, body = m.group(1), []
         elif body is not None and re.match(r"\.Lfunc_end\d+:", line):
             insns = [l for l in body if not re.match(r"\s*\.|\S+:$", l)]
-            digest = hashlib.sha256("\n".join(body).encode()).hexdigest()[:16]
+            digest = hashlib.sha256("\n".join(body).replace(sym, "<self>").encode()).hexdigest()[:16]
             found[sym] = dict(instructions=len(insns), digest=digest, **{k: res[sym].get(k) for k in RESOURCES})
             body = None
         elif body is not None:
@@ -117,19 +121,20 @@ def main():
         old, new = kernels(texts[(parent, f)]), kernels(texts[(ROOT, f)])
         for k in sorted(set(old) | set(new)):
             rows.append({"file": f, "kernel": k, "parent": old.get(k), "new": new.get(k),
-                         "identical": k in old and old[k] == new.get(k)})
+                         "identical": old[k] == new.get(k) if k in old else None})
     rev = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", a.parent], check=True, stdout=subprocess.PIPE,
                          universal_newlines=True).stdout.strip()
     doc = {"what": a.what or "Device code of %s at the parent commit and at this commit, per kernel instantiation."
-           % ", ".join(files), "how": HOW, "parent": rev, "all_identical": all(r["identical"] for r in rows),
-           "instantiations": len(rows), "kernels": rows}
+           % ", ".join(files), "how": HOW, "parent": rev,
+           "all_identical": all(r["identical"] for r in rows if r["parent"] is not None),
+           "instantiations": len(rows), "added": sum(r["parent"] is None for r in rows), "kernels": rows}
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)
         fh.write("\n")
-    differ = [r for r in rows if not r["identical"]]
+    differ = [r for r in rows if r["identical"] is False]
     for r in differ:
         print("DIFFERS", r["file"], r["kernel"])
-    print("%d instantiations in %d files, %d differ" % (len(rows), len(files), len(differ)))
+    print("%d instantiations in %d files, %d added, %d differ" % (len(rows), len(files), doc["added"], len(differ)))
     return 1 if differ else 0
 
 

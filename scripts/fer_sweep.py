@@ -24,6 +24,9 @@ columns): rate matching (MonteCarlo rate_match=, ratematch.RateMatch) -- the lis
 transmitted; a punctured one reaches the decoder as an LLR of +0, a shortened one as a known 0.  LIST:
 comma-separated indices and ranges a-b, or @FILE holding them.  Errors are counted over the positions
 that are not known, `rate` and `ebn0_db` are the rate-matched code's (K - n_known) / n_tx.
+--fused (with --quant, and --codewords random or a rate-matching list): the two modes above in the
+fixed-point decoder's own kernel (MonteCarlo fused=True) -- the same counts, and each row then carries
+`error_curve`, the error rate after every iteration over the counted positions.
 One process per GPU: `--gpus N` starts the N ranks itself (decided before any HIP call, refused
 when fewer than N GPUs are visible -- iib_project_ldpc_codes_amd/launch.py, the same plan as
 bench.py), or runs as a rank of an external torchrun; trials shard by index, counters are
@@ -41,6 +44,7 @@ parallel_simulator.py:198), --trials, or --seconds.
   python scripts/fer_sweep.py qc --base table.txt --Z 81 --schedule layered --points 0.04
   python scripts/fer_sweep.py qc --base table.txt --Z 81 --puncture-cols 0,1 --shorten @fill.txt --codewords random \
       --schedule layered --quant 6,8,2.0,6,0 --points 0.04
+  python scripts/fer_sweep.py cfg3 --schedule layered --quant 5,7,2.0,8,1 --codewords random --fused --points 0.06
 """
 import argparse
 import json
@@ -122,6 +126,9 @@ def parse(argv=None):
     ap.add_argument("--puncture-cols", type=parse_indices, default=[], metavar="LIST", help="qc: punctured block columns")
     ap.add_argument("--shorten-cols", type=parse_indices, default=[], metavar="LIST", help="qc: shortened block columns")
     ap.add_argument("--known-llr", type=float, default=1024.0, help="the LLR magnitude of a shortened position")
+    ap.add_argument("--fused", action="store_true",
+                    help="with --quant and --codewords random / a rate-matching list: channel, decode and the count of "
+                         "every iteration in one kernel (MonteCarlo fused=); the rows carry error_curve")
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks, one process per GPU (default: torchrun's WORLD_SIZE, else 1); "
                          "without WORLD_SIZE the sweep starts them itself")
@@ -153,6 +160,13 @@ def parse(argv=None):
         ap.error("--puncture-cols and --shorten-cols belong to qc (block columns)")
     if (args.puncture or args.shorten) and args.config == "ens":
         ap.error("--puncture and --shorten need a fixed code: a description names the variables of one graph")
+    if args.fused:
+        if args.quant is None:
+            ap.error("--fused needs --quant (cfg3 or qc with --schedule layered): the fused codeword mode is the "
+                     "fixed-point decoders'")
+        if args.codewords != "random" and not (args.puncture or args.shorten or args.puncture_cols or args.shorten_cols):
+            ap.error("--fused needs --codewords random or a rate-matching list: the all-zero, all-transmitted run is "
+                     "fused already")
     return args
 
 
@@ -225,7 +239,7 @@ def main(argv=None):
         else:
             mc = MonteCarlo(g, channel, p, iters, algo=algo, alpha=alpha, early_stop=True, seed=args.seed,
                             batch=batch, schedule=args.schedule, quant=args.quant, flip_threshold=args.flip_threshold,
-                            codewords=args.codewords, rate_match=rm, known_llr=args.known_llr)
+                            codewords=args.codewords, rate_match=rm, known_llr=args.known_llr, fused=args.fused)
             if rm is not None:  # the rate-matched code's rate, from the encoder's dimension where the run has one
                 K = mc.encoder.K if hasattr(mc, "encoder") else g.n - g.m
                 rate = rm.rate(K)
@@ -245,6 +259,8 @@ def main(argv=None):
                 tag += "_cw-random"
             if rm is not None:
                 tag += "_rm-" + rm.digest()[:12]
+            if args.fused:
+                tag += "_fused"
             ck = os.path.join(args.checkpoint_dir, f"{args.config}{tag}_p={p}_seed={args.seed}_B={batch}.json")
             if os.path.exists(ck):
                 mc.restore(snapshot.load(ck))
@@ -272,6 +288,8 @@ def main(argv=None):
                 out["codewords"] = "random"
             if rm is not None:
                 out["rate_match"] = dict(res["rate_match"], sha1=rm.digest(), known_llr=args.known_llr)
+            if args.fused:
+                out.update({"fused": True, "error_curve": [float(x) for x in res["error_curve"]]})
             if channel == "awgn":
                 out["ebn0_db"] = float(de.sigma_to_ebn0_db(p, rate))
             print(json.dumps(out), flush=True)
