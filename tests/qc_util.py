@@ -18,6 +18,12 @@ HAND_Z31 = [[_X, _X, _X, _X, _X, _X, _X, _X, _X, _X, _X, 30],
             [5, 0, 11, _X, _X, _X, _X, _X, 23, 30, _X, _X],
             [0, 1, 3, 7, 12, 20, 30, 9, _X, _X, _X, _X]]
 
+# mix3x12_z67: random_base(3, 12, 67, seed=5) with zero blocks at row 1 columns 9-11 and row 2 columns 2-8
+MIX3X12_MASK = [[c in cols for c in range(12)] for cols in ((), range(9, 12), range(2, 9))]
+MIX3X12_Z67 = [[44, 53, 1, 54, 31, 34, 42, 19, 65, 3, 18, 25],
+               [38, 27, 8, 3, 0, 9, 66, 12, 43, _X, _X, _X],
+               [50, 15, _X, _X, _X, _X, _X, _X, _X, 18, 29, 17]]
+
 
 @functools.lru_cache(maxsize=None)
 def code(name):
@@ -33,6 +39,17 @@ def code(name):
         return qc.random_base(2, 12, 37, seed=5)
     if name == "dense2x20_z23":
         return qc.random_base(2, 20, 23, seed=5)
+    # the shapes of the 16- and 32-wide codeword mode and of the 256-thread wide kernels (all full rank)
+    if name == "rnd3x12_z37":  # n = 444 = 4 * 111: a multiple of 4, not of 32
+        return qc.random_base(3, 12, 37, seed=5)
+    if name == "rnd3x20_z61":  # n = 1,220: 305 words of P > 4 * 64
+        return qc.random_base(3, 20, 61, seed=5)
+    if name == "mix3x12_z67":  # n = 804; block-row degrees 12, 9 and 5 on a 16-wide kernel
+        c = qc.random_base(3, 12, 67, seed=5, mask=MIX3X12_MASK)
+        assert c.base.tolist() == MIX3X12_Z67, c.base.tolist()  # a change of the generator is noticed
+        return c
+    if name == "rnd3x20_z257":  # n = 5,140: 1,285 words of P > 4 * 256; two checks per thread, a tail of one
+        return qc.random_base(3, 20, 257, seed=5)
     if name == "z1":  # the base is H itself: a 6 x 12 parity-check matrix of row degrees 4 and column degrees 2
         H = np.full((6, 12), -1)
         for c in range(12):  # column c: checks c mod 6 and (c mod 6 + 1 + c // 6) mod 6

@@ -85,6 +85,68 @@ def test_plan_rows_of_the_qc_kernels():
     assert p["name"] == "bp_layer_q_kernel<8>" and p["lds"] == 96 + 104 + 4 * 51 + 16
 
 
+WIDE = {"E": ("bp_qc_q_kernel<64,16>", 64, 16), "F": ("bp_qc_q_kernel<64,32>", 64, 32),
+        "G": ("bp_qc_q_kernel<256,16>", 256, 16), "H": ("bp_qc_q_kernel<256,32>", 256, 32)}
+
+
+@pytest.mark.parametrize("name", sorted(WIDE))
+def test_plan_rows_of_the_wide_cases(name):
+    """Cases E-H of tests/fused_cw_ref.py: the 16- and 32-wide codeword-mode kernels by name, and the
+    block curve | P | records of one or two words | plane."""
+    kernel, T, wide = WIDE[name]
+    c = qc_util.code(fr.QC_NAME[name])
+    assert (c.n % 4, c.n % 32 != 0) == (0, True)  # the one-dword codeword load; a partial plane word
+    lds = fr.curve_bytes(cu.ITERS) + 4 * ((c.n + 3) // 4) + (4 if wide == 16 else 8) * c.m + fr.plane_bytes(c.n)
+    for early_stop in (0, 1):
+        call = [(1, early_stop, 1, 0, cu.ITERS, fr.B)]
+        for has_desc in (0, 1):
+            p = fr.qc_cw_plans(c, call, has_desc)[0]
+            assert (p["name"], p["threads"], p["grid"], p["lds"]) == (kernel, T, fr.B, lds), (name, p)
+            with qc_util.table_kernels():
+                p = fr.qc_cw_plans(c, call, has_desc)[0]
+            assert (p["name"], p["threads"], p["grid"], p["lds"]) == ("bp_layer_q_kernel<%d>" % wide, 256, fr.B, lds)
+    # what the sizes are for: the masked count's second round at F and H, with a ragged tail
+    n4 = c.n // 4
+    assert (n4 > 4 * T and n4 % T != 0) == (name in "FH")
+
+
+@pytest.mark.parametrize("key", sorted(fr.FIGURES, key=str))
+def test_reference_figures_of_the_wide_cases(key):
+    name, p, early_stop, count = key
+    want = fr.counters(name, p, early_stop, count=count)
+    assert list(want[:5]) == fr.FIGURES[key]
+    assert 0 < want[1] < fr.B and fr.rows(name, p, early_stop, count=count)[2] > 0  # ties on a 1
+    if (name, count) in fr.CURVE_1_4:
+        assert list(want[5:9]) == fr.CURVE_1_4[(name, count)]
+    assert want[-1] == want[2]
+    cls, Z = fr.case(name)["cls"], qc_util.code(fr.QC_NAME[name]).Z
+    short = [c for c in range(cls.size // Z) if (cls[c * Z:(c + 1) * Z] == rr.KNOWN).all()]
+    assert (cls[:Z] == rr.PUNCT).all() and short == fr.SHORT_COLS.get(name, [])  # block column 0 punctured
+
+
+def test_reference_masks_differ_from_the_default():
+    """A kernel that ignored the count mask would give the default mask's figures: both explicit masks
+    of case G move the bit errors and curve[0], and mod3 hides one frame error."""
+    cls, p = fr.case("G")["cls"], fr.P_OF["G"]
+    base = fr.counters("G", p, True)
+    assert int(fr.mask("G", None).sum()) == 804 - 67
+    for count in ("mod3", "info"):
+        m = fr.mask("G", count)
+        assert int(m.sum()) == 536
+        got = fr.counters("G", p, True, count=count)
+        assert got[2] != base[2] and got[4] != base[4] and got[3] == base[3]
+    m = fr.mask("G", "mod3")
+    assert (m[cls == rr.KNOWN] == 1).any() and (m[cls == rr.PUNCT] == 1).any() and (m[cls == rr.TX] == 0).any()
+    assert not fr.mask("G", "info")[cls == rr.KNOWN].any()
+    assert fr.counters("G", p, True, count="mod3")[1] == base[1] - 1  # a frame whose errors all lie uncounted
+    # max_iters = 0 under mod3: the counted known positions enter, with the sign of +known_llr quantised (no error)
+    zero = fr.counters("G", p, True, iters=0, count="mod3")
+    assert zero[2] == zero[4] > 0 and zero[3] == 0 and zero[4] != fr.counters("G", p, True, iters=0)[4]
+    # the all-zero word under a description (case F): decoded and failed frames
+    z = fr.counters("F", fr.P_OF["F"], True, zero=True)
+    assert 0 < z[1] < fr.B and list(z[:5]) != fr.FIGURES[("F", 0.01, True, None)]
+
+
 # ---------------------------------------------------------- MonteCarlo(fused=True) on a stand-in
 B, ITERS = 32, 10
 

@@ -14,6 +14,25 @@ iterations, curve[0]]:
     C  BSC p = 0.05            [64, 12, 1197, 768, 4920]  (p = 0.03 and 0.04 leave no frame error)
     D  BSC p = 0.06, fixed     [64, 1, 69, 1280, 7133]
 
+Cases E-H (tests/fused_cw_ref.py says what each size is for) hold the codeword mode at 16 and 32 wide,
+on bp_qc_q_kernel at 64 and 256 threads and, under qc_util.table_kernels(), on bp_layer_q_kernel<16>
+and <32>; fr.FIGURES has their figures, with early stop (iterations 1,280 without, the rest the same):
+
+    E  BSC p = 0.02            [64, 32, 531, 835, 495]    n = 444: the one-dword codeword load, and the
+                                                          byte loads on a pointer with & 3 == 1
+    F  BSC p = 0.01            [64, 41, 962, 981, 750]    n = 1,220: two-word records, the masked count's
+                                                          second round at 64 threads; also with no codeword
+    G  BSC p = 0.015           [64, 32, 286, 791, 618]    n = 804, block column 9 shortened, block rows of
+                                                          degree 12, 9, 5; curve[1..4] = 725, 641, 433, 378
+       count mask mod3         [64, 31, 194, 791, 416]    curve[1..4] = 488, 448, 299, 264
+       count="info"            [64, 32, 215, 791, 419]
+    H  BSC p = 0.008           [64, 15, 786, 763, 2379]   n = 5,140, block column 16 shortened: the second
+                                                          round at 256 threads, two checks per thread
+G and H also run without early stop (the barrier after the count is then all that separates it from
+the next row's writes), on bp_qc_q_kernel and on the table kernels <16> and <32>; G under mod3 with
+max_iters = 0; E-H with no description and no codeword against the all-zero entry and the reference
+(the plain Monte-Carlo instantiations of the four wide shapes).
+
 BI-AWGN (r36_1000 with rate_match_ref.classes, sigma = 0.80, B = 192, QUANT): the host chain runs on
 ldpc_channel_dev's own values; the bounds are tests/test_gpu_layered_q.py::test_mc_awgn_vs_reference's.
 """
@@ -32,8 +51,12 @@ FIGURES = {("A", 0.05, True): [64, 7, 82, 330, 254], ("A", 0.05, False): [64, 7,
            ("B", 0.03, True): [64, 5, 63, 274, 170], ("B", 0.05, True): [64, 20, 238, 581, 266],
            ("B", 0.05, False): [64, 20, 238, 1280, 266], ("C", 0.05, True): [64, 12, 1197, 768, 4920],
            ("D", 0.06, False): [64, 1, 69, 1280, 7133]}
+FIGURES.update({k[:3]: v for k, v in fr.FIGURES.items() if k[3] is None})  # E-H under the default mask
 KERNEL = {"A": "bp_layer_q_kernel<8>", "B": "bp_qc_q_kernel<64,8>", "C": "bp_qc_q_kernel<256,8>",
-          "D": "bp_qc_q_kernel<256,8>"}
+          "D": "bp_qc_q_kernel<256,8>", "E": "bp_qc_q_kernel<64,16>", "F": "bp_qc_q_kernel<64,32>",
+          "G": "bp_qc_q_kernel<256,16>", "H": "bp_qc_q_kernel<256,32>"}
+TABLE = {"B": "bp_layer_q_kernel<8>", "E": "bp_layer_q_kernel<16>", "F": "bp_layer_q_kernel<32>",
+         "G": "bp_layer_q_kernel<16>", "H": "bp_layer_q_kernel<32>"}  # the same codes under qc_util.table_kernels()
 
 
 @pytest.fixture(scope="module")
@@ -64,18 +87,24 @@ def _graph(name, table=False):
     return _graphs[key]
 
 
-def _rm(name):
+def _rm(name, count=None):
+    """The case's description; count: a mask of fr.MASKS ("info" is RateMatch's own, resolved against the
+    graph's encoder; "mod3" goes in as the 0/1 mask itself)."""
     from iib_project_ldpc_codes_amd.ratematch import RateMatch
     if name == "A":
         cls = rr.classes("r36_96")
         return RateMatch(cls.size, cls == rr.PUNCT, cls == rr.KNOWN, "codeword")
-    return None if name == "D" else qc_util.code(fr.QC_NAME[name]).rate_match(punctured_cols=[0])
+    if name == "D":
+        return None
+    count = "codeword" if count is None else count if count == "info" else np.array(fr.mask(name, count))
+    return qc_util.code(fr.QC_NAME[name]).rate_match(punctured_cols=[0], shortened_cols=fr.SHORT_COLS.get(name, []),
+                                                     count=count)
 
 
-def _routed(name, early_stop, table=False):
+def _routed(name, early_stop, table=False, iters=cu.ITERS):
     """The case's plan in the codeword mode, held to the kernel it claims."""
     has_desc = name != "D"
-    call = [(1, int(early_stop), 1, 0, cu.ITERS, fr.B)]
+    call = [(1, int(early_stop), 1, 0, iters, fr.B)]
     if name == "A":
         p = fr.layer_q_cw_plans(cu.csr("r36_96"), call, has_desc)[0]
     elif table:
@@ -83,17 +112,17 @@ def _routed(name, early_stop, table=False):
             p = fr.qc_cw_plans(qc_util.code(fr.QC_NAME[name]), call, has_desc)[0]
     else:
         p = fr.qc_cw_plans(qc_util.code(fr.QC_NAME[name]), call, has_desc)[0]
-    assert p["name"] == ("bp_layer_q_kernel<8>" if table else KERNEL[name]), p
+    assert p["name"] == (TABLE[name] if table else KERNEL[name]), p
     assert p["grid"] == fr.B
     return p
 
 
-def _mc(name, p, early_stop, fused=True, table=False, quant=None, **kw):
+def _mc(name, p, early_stop, fused=True, table=False, quant=None, count=None, codewords="random", **kw):
     from iib_project_ldpc_codes_amd.decoder import Quant
     from iib_project_ldpc_codes_amd.montecarlo import MonteCarlo
     return MonteCarlo(_graph(name, table), "bsc", p, cu.ITERS, algo="minsum", schedule="layered",
                       quant=Quant(*(quant or fr.case(name)["quant"])), early_stop=early_stop, seed=cu.SEED, batch=fr.B,
-                      codewords="random", rate_match=_rm(name), fused=fused, **kw)
+                      codewords=codewords, rate_match=_rm(name, count), fused=fused, **kw)
 
 
 def _run(torch, mc, first=0, B=fr.B, stop=0):
@@ -102,10 +131,13 @@ def _run(torch, mc, first=0, B=fr.B, stop=0):
     return mc.counters.cpu().numpy()
 
 
-# ------------------------------------------------------------------ 1. A-D, bit-exact
+# ------------------------------------------------------------------ 1. A-H, bit-exact
 @pytest.mark.parametrize("name,p,early_stop,table", [
     ("A", 0.05, True, False), ("A", 0.05, False, False), ("B", 0.03, True, False), ("B", 0.05, True, False),
-    ("B", 0.05, False, False), ("B", 0.05, True, True), ("C", 0.05, True, False), ("D", 0.06, False, False)])
+    ("B", 0.05, False, False), ("B", 0.05, True, True), ("C", 0.05, True, False), ("D", 0.06, False, False),
+    ("E", 0.02, True, False), ("F", 0.01, True, False), ("G", 0.015, True, False), ("H", 0.008, True, False),
+    ("G", 0.015, False, False), ("H", 0.008, False, False), ("G", 0.015, True, True), ("F", 0.01, True, True),
+    ("G", 0.015, False, True), ("H", 0.008, False, True)])  # the table kernels <16> and <32> at a fixed count
 def test_counters_equal_the_reference(torch, name, p, early_stop, table):
     _routed(name, early_stop, table)
     want = fr.counters(name, p, early_stop)
@@ -113,6 +145,34 @@ def test_counters_equal_the_reference(torch, name, p, early_stop, table):
     assert list(want[:5]) == FIGURES[(name, p, early_stop)]
     assert 0 < want[1] < fr.B and ties > 0  # decoded and failed frames; a tie on a 1 the shortcut would miss
     got = _run(torch, _mc(name, p, early_stop, table=table))
+    np.testing.assert_array_equal(got, want)
+
+
+@pytest.mark.parametrize("count,table", [("mod3", False), ("info", False), ("mod3", True)])
+def test_count_masks_on_case_g(torch, count, table):
+    """An explicit count mask through RateMatch(count=): known and punctured positions counted,
+    transmitted ones left out (mod3), and the encoder's information positions (info).  A kernel that
+    read no mask, or took "not known" for "counted", gives the default mask's figures instead."""
+    p = fr.P_OF["G"]
+    _routed("G", True, table)
+    want, base = fr.counters("G", p, True, count=count), fr.counters("G", p, True)
+    assert list(want[:5]) == fr.FIGURES[("G", p, True, count)]
+    assert want[2] != base[2] and want[4] != base[4] and 0 < want[1] < fr.B
+    mc = _mc("G", p, True, table=table, count=count)
+    assert mc.rate_match.count == ("info" if count == "info" else "mask")
+    got = _run(torch, mc)
+    np.testing.assert_array_equal(mc.rate_match.counts(), fr.mask("G", count))  # "info": bound to the graph's encoder
+    np.testing.assert_array_equal(got, want)
+
+
+def test_a_description_without_a_codeword(torch):
+    """codewords="zero" with rate_match= and fused=True: the entry gets no codeword and means the
+    all-zero one, on the 32-wide kernel whose masked count goes a second round (case F)."""
+    p = fr.P_OF["F"]
+    _routed("F", True)
+    want = fr.counters("F", p, True, zero=True)
+    assert 0 < want[1] < fr.B and want[4] > 0
+    got = _run(torch, _mc("F", p, True, codewords="zero"))
     np.testing.assert_array_equal(got, want)
 
 
@@ -132,8 +192,9 @@ def test_expurgation_and_stop_inside_the_batch(torch):
 
 
 # ------------------------------------------------------------ 3. device identities
-@pytest.mark.parametrize("name,p", [("A", 0.05), ("B", 0.05), ("C", 0.05)])
+@pytest.mark.parametrize("name,p", [("A", 0.05), ("B", 0.05), ("C", 0.05), ("G", 0.015), ("H", 0.008)])
 def test_ends_equal_the_unfused_chain(torch, name, p):
+    _routed(name, True)
     fused = _run(torch, _mc(name, p, True))
     chain = _run(torch, _mc(name, p, True, fused=False))
     np.testing.assert_array_equal(cu.ends(fused), cu.ends(chain))
@@ -158,22 +219,68 @@ def _entry(torch, g, rm, cw, channel, param, q, B=fr.B, iters=cu.ITERS, early_st
     return rc, None if counters is False else counters.cpu().numpy()
 
 
-@pytest.mark.parametrize("name", ["A", "C"])
+@pytest.mark.parametrize("name", ["A", "C", "E", "F", "G", "H"])
 def test_no_description_no_codeword_equals_the_all_zero_entry(torch, name):
+    """E-H: the all-zero Monte-Carlo instantiations of the four wide quasi-cyclic shapes and the
+    codeword mode's unmasked count at those widths, both also against the reference."""
     from iib_project_ldpc_codes_amd import _native
     g = _graph(name)
     q = _native.Quant(2.0, 5, 7, 8, 1)
+    p = fr.P_OF.get(name, 0.05)
     for early_stop in (1, 0):
-        rc, got = _entry(torch, g, None, None, _native.CH_BSC, 0.05, ct.addressof(q), early_stop=early_stop)
+        if name in fr.P_OF:
+            c, call = qc_util.code(fr.QC_NAME[name]), [(1, early_stop, 1, 0, cu.ITERS, fr.B)]
+            assert fr.qc_cw_plans(c, call, 0)[0]["name"] == qc_util.qc_plans(c, call)[0]["name"] == KERNEL[name]
+        rc, got = _entry(torch, g, None, None, _native.CH_BSC, p, ct.addressof(q), early_stop=early_stop)
         assert rc == 0, _native.last_error()
         want = torch.zeros(_native.MC_NCOUNT + cu.ITERS + 1, dtype=torch.int64, device="cuda")
-        rc = _native.lib().ldpc_mc_layered_q_batch_dev(g.handle(), _native.CH_BSC, 0.05, cu.SEED, 0, fr.B, cu.ITERS,
+        rc = _native.lib().ldpc_mc_layered_q_batch_dev(g.handle(), _native.CH_BSC, p, cu.SEED, 0, fr.B, cu.ITERS,
                                                        ct.addressof(q), early_stop, -1, 0, want.data_ptr(), None)
         assert rc == 0, _native.last_error()
         torch.cuda.synchronize()
         # the BSC's |llr| * scale >= 0.5: no negative LLR quantises to 0, curve[0] agrees as well
         np.testing.assert_array_equal(got, want.cpu().numpy())
         assert got[4] > 0 and got[5] > 0
+        if name in fr.P_OF:
+            np.testing.assert_array_equal(got, fr.plain_counters(name, p, bool(early_stop)))
+
+
+def test_scalar_codeword_load_at_a_multiple_of_four(torch):
+    """n = 444 (case E): the aligned codeword tensor takes the one-dword load; the same bytes at offset 1
+    of a buffer of B n + 4 bytes (pointer & 3 == 1, inside an allocation of the test's) take the byte
+    loads at n mod 4 = 0.  Both equal the reference."""
+    from iib_project_ldpc_codes_amd import _native
+    c, p = fr.case("E"), fr.P_OF["E"]
+    assert c["n"] % 4 == 0
+    _routed("E", True)
+    want = fr.counters("E", p, True)
+    assert list(want[:5]) == fr.FIGURES[("E", p, True, None)]
+    g, rm, q = _graph("E"), _rm("E"), _native.Quant(2.0, 5, 7, 8, 1)
+    x = torch.from_numpy(np.array(c["x"])).cuda()
+    buf = torch.zeros(fr.B * c["n"] + 4, dtype=torch.uint8, device="cuda")
+    shifted = buf[1:1 + fr.B * c["n"]]
+    shifted.copy_(x.reshape(-1))
+    assert x.data_ptr() & 3 == 0 and shifted.data_ptr() & 3 == 1 and shifted.data_ptr() == buf.data_ptr() + 1
+    for cw in (x, shifted):
+        rc, got = _entry(torch, g, rm, cw, _native.CH_BSC, p, ct.addressof(q))
+        assert rc == 0, _native.last_error()
+        np.testing.assert_array_equal(got, want)
+
+
+def test_max_iters_zero_on_a_qc_kernel(torch):
+    """Case G under the mod3 mask with no iteration: the one entry is the count of the quantised channel
+    values, and a counted known position enters with the sign of its quantised +-known_llr."""
+    from iib_project_ldpc_codes_amd import _native
+    c, p = fr.case("G"), fr.P_OF["G"]
+    _routed("G", True, iters=0)
+    want = fr.counters("G", p, True, iters=0, count="mod3")
+    assert want.size == _native.MC_NCOUNT + 1 and want[2] == want[4] > 0 and want[3] == 0
+    assert want[4] != fr.counters("G", p, True, iters=0)[4]  # the mask is seen
+    q = _native.Quant(2.0, 5, 7, 8, 1)
+    x = torch.from_numpy(np.array(c["x"])).cuda()
+    rc, got = _entry(torch, _graph("G"), _rm("G", "mod3"), x, _native.CH_BSC, p, ct.addressof(q), iters=0)
+    assert rc == 0, _native.last_error()
+    np.testing.assert_array_equal(got, want)
 
 
 # ------------------------------------------------------------------------ 4. BI-AWGN

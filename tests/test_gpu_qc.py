@@ -13,6 +13,10 @@ The codes (tests/qc_util.py) are the smallest shapes at which the kernel can go 
                             degree-1 rule m2 = Q; mixed degrees across layers)
     dense2x12_z37           16 wide
     dense2x20_z23           32 wide, two-word records
+    mix3x12_z67             n = 804: 256 threads and 16 wide, block rows of degree 12, 9 and 5 (absent
+                            edges on a wide instantiation)
+    rnd3x20_z257            n = 5,140: 256 threads and 32 wide; Z = 257 is two checks per thread
+                            with a tail of one
     z1                      Z = 1: the base is H itself
 Every case first holds the launch plan of its own calls to the kernel name it claims.
 """
@@ -34,11 +38,12 @@ pytestmark = pytest.mark.gpu
 
 B, ITERS = 24, 20
 NAMES = ["arr36_z7", "rnd36_z64", "rnd36_z65", "arr36_z67", "arr36_z307", "hand_z31", "dense2x12_z37",
-         "dense2x20_z23", "z1"]
+         "dense2x20_z23", "z1", "mix3x12_z67", "rnd3x20_z257"]
 KERNEL = {"arr36_z7": "bp_qc_q_kernel<64,8>", "rnd36_z64": "bp_qc_q_kernel<64,8>", "rnd36_z65": "bp_qc_q_kernel<256,8>",
           "arr36_z67": "bp_qc_q_kernel<256,8>", "arr36_z307": "bp_qc_q_kernel<256,8>", "hand_z31": "bp_qc_q_kernel<64,8>",
           "dense2x12_z37": "bp_qc_q_kernel<64,16>", "dense2x20_z23": "bp_qc_q_kernel<64,32>",
-          "z1": "bp_qc_q_kernel<64,8>"}
+          "z1": "bp_qc_q_kernel<64,8>", "mix3x12_z67": "bp_qc_q_kernel<256,16>",
+          "rnd3x20_z257": "bp_qc_q_kernel<256,32>"}
 
 
 @pytest.fixture(scope="module")
@@ -213,9 +218,11 @@ def test_refusals(torch):
 
 # --------------------------------------------------------------- Monte-Carlo
 # 512 trials, so that a stop at 200 frame errors falls inside the batch: the reference (on the CPU,
-# before the assertions were written) counts 491 frame errors on arr36_z307 and 309 on arr36_z7
+# before the assertions were written) counts 491 frame errors on arr36_z307, 309 on arr36_z7 and 415
+# on mix3x12_z67 (the 256-thread, 16-wide kernel in the all-zero mode; the stop falls at trial 248)
 MC_B, MC_ITERS = 512, 20
-MC_CASES = [("arr36_z307", 0.05, (6, 8, 2.0, 6, 0)), ("arr36_z7", 0.08, (5, 7, 2.0, 8, 1))]
+MC_CASES = [("arr36_z307", 0.05, (6, 8, 2.0, 6, 0)), ("arr36_z7", 0.08, (5, 7, 2.0, 8, 1)),
+            ("mix3x12_z67", 0.02, (5, 7, 2.0, 8, 1))]
 
 
 def _mc_counters(g, p, params, early_stop, expurgation=-1, stop=0):
