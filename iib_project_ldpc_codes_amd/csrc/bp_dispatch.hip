@@ -30,6 +30,7 @@ hipError_t FloodFamily::launch(const BpPlan &p, const SoftCall &c, float *scratc
     a.E = g.E;
     a.scratch = scratch;
     a.scratch_bytes = p.scratch;
+    a.wide_io = p.wide_io;
     const bool et = c.early_stop, mc = c.mc;
     switch (p.path) {
         case BpPath::Loc: return c.algo == 0 ? launch_loc_spa(p, g, a, et, mc, s) : launch_loc_ms(p, g, a, et, mc, s);

@@ -127,6 +127,26 @@ __device__ __forceinline__ V ld_fresh(const V *p, int idx) {
     asm volatile("" : "+v"(idx));
     return p[idx];
 }
+// Row b of a [B][len] tensor as a raw buffer of `bytes` bytes: stride 0, no swizzle, and in the
+// descriptor's last word only DATA_FORMAT (bits 18:15) = 4, a 32-bit element -- a zero there is the
+// invalid format of an unbound resource; the untyped loads and stores below read no other field of
+// it.  Base = the row start (a 64-bit scalar add: a batch past 4 GB stays clear of the 32-bit lane
+// offsets).  The hardware's range check (offset >= bytes) returns 0 from a load past the row and
+// drops a store past it, so no access below carries a guard of its own; every access is aligned to
+// its own size and len % 4 = 0, so none straddles the row's end
+// (tests/test_gpu_loc_row_io.py holds this with sentinels around every output row).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void *row, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(row), 0, bytes, 0x00020000);
+}
+// Entry `entry` (a compile-time constant: the row's start) + lane of a thread-layout table of int32
+// through the table's descriptor: the row's byte offset is the instruction's scalar offset, the
+// lane's part one 32-bit byte offset (lane_bytes = 4 tid, made opaque where it is formed, so -- as
+// with ld_fresh -- nothing per entry is held across the decode, and no 64-bit VALU address is formed)
+__device__ __forceinline__ int32_t ld_row(__amdgpu_buffer_rsrc_t tab, int entry, uint32_t lane_bytes) {
+    return (int32_t)__builtin_amdgcn_raw_buffer_load_b32(tab, lane_bytes, 4 * entry, 0);
+}
 
 // Workgroup-wide OR of a per-lane predicate with ONE barrier (__syncthreads_or reduces
 // through a wave DPP chain, an LDS atomic and three barriers): each wave whose ballot is
@@ -211,15 +231,26 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
     uint32_t inf[VP];
     // packed LDS word pair of var pair v's non-local edge u (re-read per codeword and for
     // the posterior gathers: not held live outside the iteration loop, where the
-    // staging and epilogue need the VGPRs)
-    auto load_sp = [&](int v, int u) {
-        return (uint32_t)ld_fresh(a.loc_pos, (v * DVP + u) * T + tid) + base2;
+    // staging and epilogue need the VGPRs).  The fixed-count decodes' table loads go by ld_row,
+    // from a lane offset (lane_bytes) formed where the loads are
+    auto lane_bytes = [&]() {
+        uint32_t l = 4u * (uint32_t)tid;
+        asm volatile("" : "+v"(l));
+        return l;
+    };
+    auto load_sp = [&](int v, int u, uint32_t lane4 = 0u) {
+        if constexpr (CL > 0) return (uint32_t)ld_row(row_rsrc(a.loc_pos, VP * DVP * T * 4), (v * DVP + u) * T, lane4) + base2;
+        else return (uint32_t)ld_fresh(a.loc_pos, (v * DVP + u) * T + tid) + base2;
     };
     // the variable ids of the thread's var pairs (entry 2v + h; -1: none), every load issued
     // before the first use (one L2 round trip, not one per var pair; Monte-Carlo staging)
     auto load_vars = [&](int (&vv)[2 * VP]) {
 #pragma unroll
         for (int i = 0; i < 2 * VP; ++i) vv[i] = ld_fresh(a.loc_var, i * T + tid);
+    };
+    auto load_vars_row = [&](int (&vv)[2 * VP], uint32_t lane4) {
+#pragma unroll
+        for (int i = 0; i < 2 * VP; ++i) vv[i] = ld_row(row_rsrc(a.loc_var, 2 * VP * T * 4), i * T, lane4);
     };
 #pragma unroll
     for (int k = 0; k < KP; ++k) {
@@ -391,19 +422,20 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         // the two latencies overlap; the others load after it (batched there: neutral to 0.5 % slower)
         constexpr bool STG = CL > 0;
         auto load_tabs = [&]() {
+            const uint32_t lane4 = CL > 0 ? lane_bytes() : 0u;
 #pragma unroll
             for (int k = 0; k < KP; ++k) {
 #pragma unroll
-                for (int u = 0; u < DVN0; ++u) sp[2 * k][u] = load_sp(2 * k, u);
+                for (int u = 0; u < DVN0; ++u) sp[2 * k][u] = load_sp(2 * k, u, lane4);
 #pragma unroll
                 for (int u = 0; u < DVN1; ++u)
-                    if (!(chained(2 * k + 1) && u == DVN1 - 1)) sp[2 * k + 1][u] = load_sp(2 * k + 1, u);
+                    if (!(chained(2 * k + 1) && u == DVN1 - 1)) sp[2 * k + 1][u] = load_sp(2 * k + 1, u, lane4);
             }
         };
         int vv[2 * VP];
         if constexpr (STG) {
             load_tabs();
-            load_vars(vv);
+            load_vars_row(vv, lane_bytes());
         }
         int err0 = 0;
         if constexpr (MC) {
@@ -426,16 +458,34 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             if constexpr (STG) {
                 // every variable is the local one of one check, so n <= 2 VP T: the copy is 2 VP
                 // loads per thread, all in flight at once (one HBM round trip; the loop below
-                // takes one per unrolled trip); a thread's entries past n read variable n - 1
-                float r[2 * VP];
-                const float *lb = a.llr + (size_t)b * n;
-                int t = tid;
+                // takes one per unrolled trip),
+                // through the row's descriptor (row_rsrc), so no load carries a clamp and no LDS write
+                // a guard: what a thread reads past the row (zeros) goes to the spare words behind
+                // variable n - 1 (loc_spare_ok).  wide_io (the plan: rows 16-byte aligned): VP / 2
+                // groups of four consecutive variables, 16 bytes a load and an LDS write
+                const __amdgpu_buffer_rsrc_t rl = row_rsrc(a.llr + (size_t)b * n, 4 * n);
+                uint32_t t = (uint32_t)tid;
                 asm volatile("" : "+v"(t));  // as ld_fresh: no index per entry held across the decode
+                if (a.wide_io) {
+                    f32x4 r[VP / 2];
 #pragma unroll
-                for (int i = 0; i < 2 * VP; ++i) r[i] = lb[min(t + i * T, n - 1)];
+                    for (int j = 0; j < VP / 2; ++j)
+                        r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rl, 16u * (t + j * T), 0, 0));
 #pragma unroll
-                for (int i = 0; i < 2 * VP; ++i)
-                    if (t + i * T < n) msg[t + i * T] = to_msg<ALGO>(r[i]);
+                    for (int j = 0; j < VP / 2; ++j) {
+                        f32x4 w;
+                        w.x = to_msg<ALGO>(r[j].x); w.y = to_msg<ALGO>(r[j].y);
+                        w.z = to_msg<ALGO>(r[j].z); w.w = to_msg<ALGO>(r[j].w);
+                        *reinterpret_cast<f32x4 *>(msg + min(4u * (t + j * T), (uint32_t)n)) = w;
+                    }
+                } else {
+                    float r[2 * VP];
+#pragma unroll
+                    for (int i = 0; i < 2 * VP; ++i)
+                        r[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rl, 4u * (t + i * T), 0, 0));
+#pragma unroll
+                    for (int i = 0; i < 2 * VP; ++i) msg[min(t + i * T, (uint32_t)n)] = to_msg<ALGO>(r[i]);
+                }
             } else {
                 for (int v = tid; v < n; v += T) msg[v] = to_msg<ALGO>(a.llr[(size_t)b * n + v]);
             }
@@ -447,8 +497,17 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         }
         if constexpr (!STG) load_tabs();
         float2 L[VP];  // SPA: E = 2^channel (clamped); min-sum: channel LLR
-        if constexpr (MC || STG) {
-            if constexpr (!STG) load_vars(vv);
+        if constexpr (STG) {
+            // a thread t < Tq holds all of its 2 VP variables, any other thread none
+            // (build_loc_chain_layout): one branch around the reads, as around the check phase
+#pragma unroll
+            for (int v = 0; v < VP; ++v) L[v] = make_float2(0.0f, 0.0f);
+            if (tid < a.loc_cls_q[1]) {
+#pragma unroll
+                for (int v = 0; v < VP; ++v) L[v] = make_float2(msg[vv[2 * v]], msg[vv[2 * v + 1]]);
+            }
+        } else if constexpr (MC) {
+            load_vars(vv);
 #pragma unroll
             for (int v = 0; v < VP; ++v)
                 L[v] = make_float2(vv[2 * v] >= 0 ? msg[vv[2 * v]] : 0.0f, vv[2 * v + 1] >= 0 ? msg[vv[2 * v + 1]] : 0.0f);
@@ -771,7 +830,7 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         int pid[2 * VP];
         bool clamped = false;
         if constexpr (FIX) {
-            load_vars(pid);
+            load_vars_row(pid, lane_bytes());
             if constexpr (SPA) {
 #pragma unroll
                 for (int v = 0; v < VP; ++v)
@@ -834,32 +893,73 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             }
         }
         __syncthreads();  // all gathers done before the staging overwrites messages
+        if constexpr (FIX && CL > 0) {  // the thread holds all of its variables or none (see the staging)
+            if (tid < a.loc_cls_q[1]) {
 #pragma unroll
-        for (int v = 0; v < VP; ++v) {
-            int v0, v1;
-            if constexpr (FIX) {
-                v0 = pid[2 * v];
-                v1 = pid[2 * v + 1];
-            } else {
-                v0 = ld_fresh(a.loc_var, (v * 2 + 0) * T + tid);
-                v1 = ld_fresh(a.loc_var, (v * 2 + 1) * T + tid);
+                for (int v = 0; v < VP; ++v) {
+                    msg[pid[2 * v]] = pr[v].x;
+                    msg[pid[2 * v + 1]] = pr[v].y;
+                }
             }
-            if (v0 >= 0) msg[v0] = pr[v].x;
-            if (v1 >= 0) msg[v1] = pr[v].y;
+        } else if constexpr (FIX) {  // an absent variable (-1) writes the spare word behind variable n - 1
+#pragma unroll
+            for (int v = 0; v < VP; ++v) {
+                msg[min((uint32_t)pid[2 * v], (uint32_t)n)] = pr[v].x;
+                msg[min((uint32_t)pid[2 * v + 1], (uint32_t)n)] = pr[v].y;
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < VP; ++v) {
+                const int v0 = ld_fresh(a.loc_var, (v * 2 + 0) * T + tid);
+                const int v1 = ld_fresh(a.loc_var, (v * 2 + 1) * T + tid);
+                if (v0 >= 0) msg[v0] = pr[v].x;
+                if (v1 >= 0) msg[v1] = pr[v].y;
+            }
         }
         __syncthreads();
-        if constexpr (FIX) {  // n <= 2 VP T (see the LLR copy): every LDS read issued before the first store
-            float o[2 * VP];
-            int t = tid;
+        if constexpr (FIX) {
+            // n <= 2 VP T (see the LLR copy); rows through their descriptors as there: every LDS read
+            // issued before the first store, a read past variable n - 1 takes the spare words and its
+            // store is dropped.  wide_io: 16 bytes of posteriors and four packed decisions a store
+            uint32_t t = (uint32_t)tid;
             asm volatile("" : "+v"(t));  // as ld_fresh: no index per entry held across the decode
+            if (a.wide_io) {
+                f32x4 o[VP / 2];
 #pragma unroll
-            for (int i = 0; i < 2 * VP; ++i) o[i] = msg[min(t + i * T, n - 1)];
+                for (int j = 0; j < VP / 2; ++j)
+                    o[j] = *reinterpret_cast<const f32x4 *>(msg + min(4u * (t + j * T), (uint32_t)n));
+                if (a.post) {
+                    const __amdgpu_buffer_rsrc_t rp = row_rsrc(a.post + (size_t)b * n, 4 * n);
 #pragma unroll
-            for (int i = 0; i < 2 * VP; ++i) {
-                const int v = t + i * T;
-                if (v < n) {
-                    if (a.post) a.post[(size_t)b * n + v] = o[i] * Domain<ALGO>::out;
-                    if (a.hard) a.hard[(size_t)b * n + v] = (uint8_t)(o[i] < 0.0f);
+                    for (int j = 0; j < VP / 2; ++j)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[j] * Domain<ALGO>::out), rp,
+                                                               16u * (t + j * T), 0, 0);
+                }
+                if (a.hard) {
+                    const __amdgpu_buffer_rsrc_t rh = row_rsrc(a.hard + (size_t)b * n, n);
+#pragma unroll
+                    for (int j = 0; j < VP / 2; ++j) {
+                        const uint32_t h = (uint32_t)(o[j].x < 0.0f) | (uint32_t)(o[j].y < 0.0f) << 8 |
+                                           (uint32_t)(o[j].z < 0.0f) << 16 | (uint32_t)(o[j].w < 0.0f) << 24;
+                        __builtin_amdgcn_raw_buffer_store_b32(h, rh, 4u * (t + j * T), 0, 0);
+                    }
+                }
+            } else {
+                float o[2 * VP];
+#pragma unroll
+                for (int i = 0; i < 2 * VP; ++i) o[i] = msg[min(t + i * T, (uint32_t)n)];
+                if (a.post) {
+                    const __amdgpu_buffer_rsrc_t rp = row_rsrc(a.post + (size_t)b * n, 4 * n);
+#pragma unroll
+                    for (int i = 0; i < 2 * VP; ++i)
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[i] * Domain<ALGO>::out), rp,
+                                                              4u * (t + i * T), 0, 0);
+                }
+                if (a.hard) {
+                    const __amdgpu_buffer_rsrc_t rh = row_rsrc(a.hard + (size_t)b * n, n);
+#pragma unroll
+                    for (int i = 0; i < 2 * VP; ++i)
+                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(o[i] < 0.0f), rh, t + i * T, 0, 0);
                 }
             }
         } else {

@@ -42,7 +42,7 @@ namespace {
 
 // messages | MC: per-iteration curve (16-byte padded) | min-sum MC: syndrome bits
 size_t loc_lds_bytes(const GraphShape &g, int iters, bool mc, bool syn) {
-    return pad16((size_t)std::max(g.loc_words + 64, g.n) * 4) + (mc ? curve_bytes(iters) : 0) +
+    return pad16(loc_msg_words(g.loc_words, g.n) * 4) + (mc ? curve_bytes(iters) : 0) +
            (syn ? (size_t)((g.m + 31) / 32) * 4 : 0);
 }
 // Early stop with posteriors on bp_loc_kernel: a VP x T float2 slab per workgroup
@@ -96,11 +96,11 @@ BpPath choose_path(const GraphShape &g, int iters, bool et, bool mc, int algo, b
     const bool lds36_ms = LDPC_LDS36_MINSUM && algo == 1 && g.lane_T && g.dv == 3 && g.dc == 6 && g.loc_T != 512;
     const bool one_cls = loc_variant(g) == kLocReg36;  // the one-class (3,6) instantiation
     // early stop with posteriors stages n posteriors + n decision bytes in the message LDS
-    const bool ep_ok = LDPC_LOC_ET_POST && (size_t)std::max(g.loc_words + 64, g.n) * 4 >= (size_t)g.n * 5;
+    const bool ep_ok = LDPC_LOC_ET_POST && loc_msg_words(g.loc_words, g.n) * 4 >= (size_t)g.n * 5;
     const bool mode_ok = mc ? (algo == 0 || (LDPC_LOC_MSMC && one_cls))
                             : (!et || (LDPC_LOC_HARD_ET && (hard_only || ep_ok) && (algo == 0 || one_cls)));
     const bool mset = et && algo == 1;
-    if (LDPC_LOC && mode_ok && iters > 0 && !lds36_ms && loc_variant(g) != kLocNone &&
+    if (LDPC_LOC && mode_ok && iters > 0 && !lds36_ms && loc_variant(g) != kLocNone && loc_spare_ok(g.loc_words, g.n) &&
         loc_lds_bytes(g, iters, mc || mset, mset) <= kLdsMax - 2048)
         return BpPath::Loc;
     if (g.lane_T && g.dv == 3 && g.dc == 6 && lds36_bytes(g, iters, et, mc) <= kLdsMax - 2048)
@@ -130,8 +130,8 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
             p.lds = loc_lds_bytes(g, iters, mc || mset, mset);
             // fixed-count sum-product on a graph with a chained layout: its instantiation, its
             // tables and its (smaller) message LDS; every other mode keeps the plain layout
-            p.chain = LDPC_LOC_CHAIN && g.chn_Tq > 0 && algo == 0 && !et && !mc;
-            if (p.chain) p.lds = pad16((size_t)std::max(g.chn_words + 64, g.n) * 4);
+            p.chain = LDPC_LOC_CHAIN && g.chn_Tq > 0 && algo == 0 && !et && !mc && loc_spare_ok(g.chn_words, g.n);
+            if (p.chain) p.lds = pad16(loc_msg_words(g.chn_words, g.n) * 4);
             // early stop with posteriors: persistent workgroups (two per CU, the most any
             // bp_loc_kernel shape keeps resident), each with a slab; early stop without: the same
             // grid on the counter alone
@@ -188,6 +188,13 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
         p.scratch += sizeof(uint32_t);
     }
     return p;
+}
+
+bool bp_wide_io(const BpPlan &p, const GraphShape &g, bool early_stop, bool mc, const void *llr, const void *post,
+                const void *hard, bool narrow) {
+    auto aligned = [](const void *q, uintptr_t to) { return (reinterpret_cast<uintptr_t>(q) & (to - 1)) == 0; };
+    return p.path == BpPath::Loc && !early_stop && !mc && !narrow && g.n % 4 == 0 && aligned(llr, 16) &&
+           aligned(post, 16) && aligned(hard, 4);
 }
 
 // bp_ens_kernel: the shape alone decides (every graph of the batch is (dv, dc) regular on n

@@ -115,6 +115,10 @@ static SoftCall decode_call(int B, int max_iters, int algo, float alpha, int ear
                             uint8_t *hard, int32_t *its) {
     SoftCall c{B, max_iters, algo, alpha, early_stop != 0, false};
     c.llr = llr, c.post = post, c.hard = hard, c.its = its;
+    // LDPC_NO_WIDE_IO=1, read per call: the fixed-count bp_loc_kernel decodes move their rows 4 bytes
+    // and 1 byte at a time whatever the alignment (tests hold the 16-byte path to this one)
+    const char *nowide = getenv("LDPC_NO_WIDE_IO");
+    c.narrow_io = nowide && nowide[0] == '1';
     return c;
 }
 // The call of a fused Monte-Carlo batch (mc_entry gives it trial and its)
@@ -347,6 +351,36 @@ int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const
                        char *names) {
     return graph_plans(check_ptr, check_var, var_ptr, var_slot, n, m, count, calls, cus, out, names, bp_plan, false,
                        &BpPlan::lds_slots);
+}
+
+// The same with the calls' row pointers (addresses only, nothing is read through them; FloodFamily::plan's
+// steps): calls[i] = {B, iters, algo, early_stop, mc, llr, post, hard, narrow}, want_post = post != 0;
+// out + 11 i = ldpc_debug_bp_plan's nine, then wide_io and the words of bp_loc_kernel's message LDS
+// (0 on another path).
+int ldpc_debug_bp_plan_io(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                          const int32_t *var_slot, int n, int m, int count, const int64_t *calls, int cus, int64_t *out,
+                          char *names) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out && names)) && cus > 0, "bad plan arguments");
+    HostGraph h;
+    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
+    GraphShape g;
+    HostLayouts L;
+    host_layouts(h, g, L, true, layout_options());
+    for (int i = 0; i < count; ++i) {
+        const int64_t *c = calls + 9 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        const bool et = c[3] != 0, mc = c[4] != 0;
+        BpPlan p = bp_plan(g, (int)c[0], (int)c[1], (int)c[2], et, mc, c[6] != 0, cus);
+        p.wide_io = bp_wide_io(p, g, et, mc, reinterpret_cast<const void *>(c[5]), reinterpret_cast<const void *>(c[6]),
+                               reinterpret_cast<const void *>(c[7]), c[8] != 0);
+        int64_t *o = out + 11 * (size_t)i;
+        o[0] = (int64_t)p.path; o[1] = p.threads; o[2] = p.grid; o[3] = (int64_t)p.lds; o[4] = p.lds_slots;
+        o[5] = p.persistent; o[6] = (int64_t)p.slab; o[7] = p.counter; o[8] = (int64_t)p.scratch;
+        o[9] = p.wide_io;
+        o[10] = p.path == BpPath::Loc ? (int64_t)loc_msg_words(p.chain ? g.chn_words : g.loc_words, g.n) : 0;
+        snprintf(names + 64 * (size_t)i, 64, "%s", p.name);
+    }
+    return LDPC_OK;
 }
 
 // The launch plans (bec_plan) of `count` BEC calls on an (n, m) graph of check degree dc (0:

@@ -38,6 +38,7 @@ struct BpArgs {
     // LDS kernel lane layout (ldpc_graph::lane_var / lane_slot)
     const int32_t *lane_var, *lane_slot;
     int lds_slots;  // generic GMEM kernel: message slots [0, lds_slots) kept in LDS
+    int wide_io;    // bp_loc_kernel fixed count: 16-byte row I/O (BpPlan::wide_io); here, in what was padding: no other member moves
     // irregular kernel layout (ldpc_graph::irr_*)
     const int32_t *irr_lane, *irr_cdeg;
     int irr_KC, irr_S, irr_P;

@@ -212,6 +212,14 @@ namespace ldpc {
 
 void set_error(const std::string &msg);
 constexpr size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }  // LDS carves keep 16-byte alignment
+// bp_loc_kernel's message LDS in words: the layout's message words and its 64 dummy words, or the
+// n staged channel values / posteriors, whichever is more.  The plan takes the kernel only for a
+// layout that leaves kLocSpare spare words behind the n staged values (loc_spare_ok; every layout
+// the builders make does: a variable has a non-local edge): the fixed-count decodes' unguarded row
+// I/O sends what lies past variable n - 1 there.
+constexpr int kLocSpare = 4;
+constexpr size_t loc_msg_words(int words, int n) { return (size_t)(words + 64 > n ? words + 64 : n); }
+constexpr bool loc_spare_ok(int words, int n) { return words + 64 >= n + kLocSpare; }
 
 // The launch plan of one BEC call (bec_plan.cpp): which kernel runs and everything its launch
 // needs, decided in one host-only function; bec.hip and peel.hip launch what it says.
@@ -282,6 +290,7 @@ struct BpPlan {
     size_t lds = 0;             // dynamic LDS bytes
     int lds_slots = 0;          // bp_generic_kernel / bp_ens_kernel <*,gmem>: message slots [0, lds_slots) kept in LDS
     bool chain = false;         // bp_loc_kernel: the chained layout's instantiation and tables
+    bool wide_io = false;       // bp_loc_kernel, fixed count: 16-byte row I/O (bp_wide_io; FloodFamily::plan sets it)
     bool persistent = false;    // bp_loc_kernel: the grid pulls codewords from a counter in scratch
     size_t slab = 0;            // bytes of per-workgroup slabs at the start of scratch (0: none)
     long counter = -1;          // byte offset of the work counter in scratch (-1: none)
@@ -291,6 +300,12 @@ struct BpPlan {
 // cus: compute units of the device (device_cus()); mc: fused-channel Monte-Carlo; want_post: a
 // decode that returns posteriors.
 BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool early_stop, bool mc, bool want_post, int cus);
+// Whether the fixed-count decode of plan p (bp_loc_kernel) moves its rows 16 bytes at a time: n % 4
+// = 0 (every local-edge layout's is), so row b of llr and post starts 16-byte aligned and row b of
+// hard 4-byte aligned exactly when the tensor does; a null post or hard counts as aligned.
+// Otherwise, or when narrow is set (LDPC_NO_WIDE_IO=1), 4-byte and 1-byte accesses.
+bool bp_wide_io(const BpPlan &p, const GraphShape &g, bool early_stop, bool mc, const void *llr, const void *post,
+                const void *hard, bool narrow);
 // The plan of an ensemble call (bp_ens_kernel, bp_ens.hip): word b decodes on its own (dv, dc)
 // regular graph, rows b of the sampler's two lists.  One workgroup owns one block
 //   messages float[E] | channel LLRs float[n] | cross index int32[E]
@@ -372,6 +387,7 @@ struct SoftCall {
     void *post = nullptr;  // float [B][n]; int8 for the fixed-point family; nullptr: no posteriors
     uint8_t *hard = nullptr;
     int32_t *its = nullptr;  // [B]
+    bool narrow_io = false;  // LDPC_NO_WIDE_IO=1 (capi.cpp): no 16-byte row I/O (tests hold the wide path to the narrow one)
     ChanArgs ch{};
     uint64_t first_cw = 0;
     int32_t *trial = nullptr;  // [B][max_iters+1] per-trial curves (then launch_mc_reduce)
@@ -389,7 +405,9 @@ struct SoftCall {
 struct FloodFamily {  // flooding on a fixed code (bp_dispatch.hip and the kernel files behind it)
     const ldpc_graph &g;
     BpPlan plan(const SoftCall &c, int cus) const {
-        return bp_plan(g, c.B, c.max_iters, c.algo, c.early_stop, c.mc, c.post != nullptr, cus);
+        BpPlan p = bp_plan(g, c.B, c.max_iters, c.algo, c.early_stop, c.mc, c.post != nullptr, cus);
+        p.wide_io = bp_wide_io(p, g, c.early_stop, c.mc, c.llr, c.post, c.hard, c.narrow_io);
+        return p;
     }
     hipError_t launch(const BpPlan &p, const SoftCall &c, float *scratch, hipStream_t s) const;
 };

@@ -725,5 +725,10 @@ bool build_loc_chain_layout(int n, int m, const std::vector<int32_t> &cptr, cons
         info |= 1u << (16 + 4 * h + jl);
         C.info[(size_t)vi * T + t] |= (int32_t)info;
     }
+    // n = 2 VP Tq: a thread t < Tq holds a variable in every one of its 2 VP entries, any other
+    // thread in none (the kernel puts one branch around a thread's reads and writes of them)
+    for (int t = 0; t < T; ++t)
+        for (int i = 0; i < 2 * VP; ++i)
+            if ((C.var[(size_t)i * T + t] >= 0) != (t < Tq)) return false;
     return true;
 }

@@ -776,6 +776,19 @@ int ldpc_debug_bp_plan(const int32_t *check_ptr, const int32_t *check_var, const
                        char *names);
 
 /*
+ * Host-only: ldpc_debug_bp_plan with the calls' device pointers -- their addresses alone, nothing is
+ * read through them.  calls[i] int64[9] = {B, iters, algo, early_stop, mc, llr, post, hard, narrow}
+ * (post = 0: no posteriors asked for; narrow: LDPC_NO_WIDE_IO=1); out[i] int64[11] =
+ * ldpc_debug_bp_plan's nine, then wide_io (1: bp_loc_kernel's fixed-count decode moves its rows 16
+ * bytes at a time: llr and post 16-byte aligned, hard 4-byte aligned, a null one counts as aligned)
+ * and the words of bp_loc_kernel's message LDS (at least n + 4: the spare words behind the staged
+ * rows; 0 on another path).
+ */
+int ldpc_debug_bp_plan_io(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                          const int32_t *var_slot, int n, int m, int count, const int64_t *calls, int cus, int64_t *out,
+                          char *names);
+
+/*
  * Host-only: the launch plans of `count` ensemble soft-decoding calls on the (n, dv, dc)
  * shape (csrc/bp_plan.cpp bp_ens_plan).  calls[i] = {B, iters, algo, early_stop, mc,
  * want_post}; out[i] int64[9] = {path, threads, grid, LDS bytes, lds_slots, 0, slab bytes, -1,
