@@ -193,8 +193,8 @@ __device__ __forceinline__ uint32_t block_count(int pred, uint32_t *flag, int pa
 // VGPRs), so one workgroup's barrier waits overlap the other's work; else one workgroup
 constexpr int loc_waves_per_simd(int T, int KP) { return T == 512 && KP <= 5 ? 4 : 1; }
 
-// CL > 0: the chained layout (loc_layout.cpp) with CL = KP - 1 chain links per thread: threads
-// t < Tq (a.loc_cls_q[1]) own pairs t + k Tq; pair slot k >= 1 takes its input slot 2 from
+// CL > 0: the chained layout (loc_layout.cpp) with CL = KP - 1 chain links per thread, launched
+// Tq (a.loc_cls_q[1]) threads wide: thread t owns pairs t + k Tq; pair slot k >= 1 takes its input slot 2 from
 // chain[k - 1] and has three LDS inputs (class 1: rows of (KP - 1) Tq pairs from word
 // a.loc_cls_w[1]); var pair 2k + 1, k < CL, has one LDS edge (row 0 of loc_pos) and chain[k].
 // Fixed-count sum-product only.
@@ -223,6 +223,11 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
     float *msg = reinterpret_cast<float *>(smem);
     const int tid = threadIdx.x;
     const int n = a.n, iters = a.max_iters;
+    // the launch width: the chained instantiation runs Tq threads (launch_loc_modes), each with all
+    // KP pair slots and its 4 KP variables -- no lane of it tests tid < Tq, a part-filled last wave
+    // is the hardware's EXEC mask, and what the workgroup does together strides by Wd.  T stays
+    // the stride of the thread-layout tables.
+    const int Wd = CL > 0 ? a.loc_cls_q[1] : T;
     const int lpos0 = (int)((uint32_t)(size_t)(lds_u8 *)smem >> 2);
     const uint32_t base2 = (uint32_t)lpos0 | ((uint32_t)lpos0 << 16);
     constexpr bool SPA = ALGO == 0;
@@ -456,13 +461,14 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             if constexpr (MSET)
                 for (int i = tid; i < nsw; i += T) syn[i] = 0u;
             if constexpr (STG) {
-                // every variable is the local one of one check, so n <= 2 VP T: the copy is 2 VP
-                // loads per thread, all in flight at once (one HBM round trip; the loop below
-                // takes one per unrolled trip),
-                // through the row's descriptor (row_rsrc), so no load carries a clamp and no LDS write
-                // a guard: what a thread reads past the row (zeros) goes to the spare words behind
-                // variable n - 1 (loc_spare_ok).  wide_io (the plan: rows 16-byte aligned): VP / 2
-                // groups of four consecutive variables, 16 bytes a load and an LDS write
+                // every variable is the local one of one check and every thread holds 2 VP of them, so
+                // n = 2 VP Wd: the copy is 2 VP loads per thread, all in flight at once (one HBM round
+                // trip; the loop below takes one per unrolled trip), striding by the launch width, and
+                // covers the row exactly -- nothing is read or staged past variable n - 1.  The rows go
+                // through their descriptor (row_rsrc); group j's offset j Wd is the instruction's scalar
+                // offset (as ld_row's entry), the lane's part one 32-bit byte offset.  wide_io (the
+                // plan: rows 16-byte aligned): VP / 2 groups of four consecutive variables, 16 bytes a
+                // load and an LDS write
                 const __amdgpu_buffer_rsrc_t rl = row_rsrc(a.llr + (size_t)b * n, 4 * n);
                 uint32_t t = (uint32_t)tid;
                 asm volatile("" : "+v"(t));  // as ld_fresh: no index per entry held across the decode
@@ -470,21 +476,21 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
                     f32x4 r[VP / 2];
 #pragma unroll
                     for (int j = 0; j < VP / 2; ++j)
-                        r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rl, 16u * (t + j * T), 0, 0));
+                        r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rl, 16u * t, 16 * j * Wd, 0));
 #pragma unroll
                     for (int j = 0; j < VP / 2; ++j) {
                         f32x4 w;
                         w.x = to_msg<ALGO>(r[j].x); w.y = to_msg<ALGO>(r[j].y);
                         w.z = to_msg<ALGO>(r[j].z); w.w = to_msg<ALGO>(r[j].w);
-                        *reinterpret_cast<f32x4 *>(msg + min(4u * (t + j * T), (uint32_t)n)) = w;
+                        *reinterpret_cast<f32x4 *>(msg + 4u * (t + (uint32_t)(j * Wd))) = w;
                     }
                 } else {
                     float r[2 * VP];
 #pragma unroll
                     for (int i = 0; i < 2 * VP; ++i)
-                        r[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rl, 4u * (t + i * T), 0, 0));
+                        r[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rl, 4u * t, 4 * i * Wd, 0));
 #pragma unroll
-                    for (int i = 0; i < 2 * VP; ++i) msg[min(t + i * T, (uint32_t)n)] = to_msg<ALGO>(r[i]);
+                    for (int i = 0; i < 2 * VP; ++i) msg[t + (uint32_t)(i * Wd)] = to_msg<ALGO>(r[i]);
                 }
             } else {
                 for (int v = tid; v < n; v += T) msg[v] = to_msg<ALGO>(a.llr[(size_t)b * n + v]);
@@ -498,14 +504,9 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         if constexpr (!STG) load_tabs();
         float2 L[VP];  // SPA: E = 2^channel (clamped); min-sum: channel LLR
         if constexpr (STG) {
-            // a thread t < Tq holds all of its 2 VP variables, any other thread none
-            // (build_loc_chain_layout): one branch around the reads, as around the check phase
+            // every thread of the launch holds all of its 2 VP variables (build_loc_chain_layout)
 #pragma unroll
-            for (int v = 0; v < VP; ++v) L[v] = make_float2(0.0f, 0.0f);
-            if (tid < a.loc_cls_q[1]) {
-#pragma unroll
-                for (int v = 0; v < VP; ++v) L[v] = make_float2(msg[vv[2 * v]], msg[vv[2 * v + 1]]);
-            }
+            for (int v = 0; v < VP; ++v) L[v] = make_float2(msg[vv[2 * v]], msg[vv[2 * v + 1]]);
         } else if constexpr (MC) {
             load_vars(vv);
 #pragma unroll
@@ -647,21 +648,20 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             // ---- check phase ----
             if (LDPC_LOC_PRIO) __builtin_amdgcn_s_setprio(0);
             if constexpr (CL > 0) {
-                // threads t < Tq own all KP pair slots: one branch around the phase
-                const int Tq = a.loc_cls_q[1];
-                if (tid < Tq) {
+                // every thread of the launch owns all KP pair slots: no lane test around the phase
+                // (one would cost the loop a register copy per value it rewrites, at the join)
+                const int Tq = Wd;
 #pragma unroll
-                    for (int k = 0; k < KP; ++k) {
-                        int i = tid + (k > 0 ? (k - 1) * Tq : 0);  // index in the pair's class
-                        asm volatile("" : "+v"(i));  // recomputed per iteration, as q below
-                        if (k == 0)
-                            loc_check_pair<DLO, ALGO>(msg, 0, Tq, i, loc[0], loc[1], a.alpha);
-                        else
-                            loc_check_pair<DLO, ALGO, false, false, CL>(msg, a.loc_cls_w[1], (KP - 1) * Tq, i, loc[2 * k],
-                                                                        loc[2 * k + 1], a.alpha, 0u, &chain[k - 1]);
-                        if (LDPC_LOC_CGROUP > 0 && k % LDPC_LOC_CGROUP == LDPC_LOC_CGROUP - 1)
-                            __builtin_amdgcn_sched_barrier(0);
-                    }
+                for (int k = 0; k < KP; ++k) {
+                    int i = tid + (k > 0 ? (k - 1) * Tq : 0);  // index in the pair's class
+                    asm volatile("" : "+v"(i));  // recomputed per iteration, as q below
+                    if (k == 0)
+                        loc_check_pair<DLO, ALGO>(msg, 0, Tq, i, loc[0], loc[1], a.alpha);
+                    else
+                        loc_check_pair<DLO, ALGO, false, false, CL>(msg, a.loc_cls_w[1], (KP - 1) * Tq, i, loc[2 * k],
+                                                                    loc[2 * k + 1], a.alpha, 0u, &chain[k - 1]);
+                    if (LDPC_LOC_CGROUP > 0 && k % LDPC_LOC_CGROUP == LDPC_LOC_CGROUP - 1)
+                        __builtin_amdgcn_sched_barrier(0);
                 }
             }
 #pragma unroll
@@ -893,13 +893,11 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             }
         }
         __syncthreads();  // all gathers done before the staging overwrites messages
-        if constexpr (FIX && CL > 0) {  // the thread holds all of its variables or none (see the staging)
-            if (tid < a.loc_cls_q[1]) {
+        if constexpr (FIX && CL > 0) {  // every thread of the launch holds all of its variables (see the staging)
 #pragma unroll
-                for (int v = 0; v < VP; ++v) {
-                    msg[pid[2 * v]] = pr[v].x;
-                    msg[pid[2 * v + 1]] = pr[v].y;
-                }
+            for (int v = 0; v < VP; ++v) {
+                msg[pid[2 * v]] = pr[v].x;
+                msg[pid[2 * v + 1]] = pr[v].y;
             }
         } else if constexpr (FIX) {  // an absent variable (-1) writes the spare word behind variable n - 1
 #pragma unroll
@@ -917,7 +915,51 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             }
         }
         __syncthreads();
-        if constexpr (FIX) {
+        if constexpr (FIX && CL > 0) {
+            // n = 2 VP Wd (see the LLR copy): the same strides by the launch width cover the rows exactly,
+            // group j's offset the stores' scalar offset; every LDS read issued before the first store
+            uint32_t t = (uint32_t)tid;
+            asm volatile("" : "+v"(t));  // as ld_fresh: no index per entry held across the decode
+            if (a.wide_io) {
+                f32x4 o[VP / 2];
+#pragma unroll
+                for (int j = 0; j < VP / 2; ++j)
+                    o[j] = *reinterpret_cast<const f32x4 *>(msg + 4u * (t + (uint32_t)(j * Wd)));
+                if (a.post) {
+                    const __amdgpu_buffer_rsrc_t rp = row_rsrc(a.post + (size_t)b * n, 4 * n);
+#pragma unroll
+                    for (int j = 0; j < VP / 2; ++j)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[j] * Domain<ALGO>::out), rp,
+                                                               16u * t, 16 * j * Wd, 0);
+                }
+                if (a.hard) {
+                    const __amdgpu_buffer_rsrc_t rh = row_rsrc(a.hard + (size_t)b * n, n);
+#pragma unroll
+                    for (int j = 0; j < VP / 2; ++j) {
+                        const uint32_t h = (uint32_t)(o[j].x < 0.0f) | (uint32_t)(o[j].y < 0.0f) << 8 |
+                                           (uint32_t)(o[j].z < 0.0f) << 16 | (uint32_t)(o[j].w < 0.0f) << 24;
+                        __builtin_amdgcn_raw_buffer_store_b32(h, rh, 4u * t, 4 * j * Wd, 0);
+                    }
+                }
+            } else {
+                float o[2 * VP];
+#pragma unroll
+                for (int i = 0; i < 2 * VP; ++i) o[i] = msg[t + (uint32_t)(i * Wd)];
+                if (a.post) {
+                    const __amdgpu_buffer_rsrc_t rp = row_rsrc(a.post + (size_t)b * n, 4 * n);
+#pragma unroll
+                    for (int i = 0; i < 2 * VP; ++i)
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[i] * Domain<ALGO>::out), rp, 4u * t,
+                                                              4 * i * Wd, 0);
+                }
+                if (a.hard) {
+                    const __amdgpu_buffer_rsrc_t rh = row_rsrc(a.hard + (size_t)b * n, n);
+#pragma unroll
+                    for (int i = 0; i < 2 * VP; ++i)
+                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(o[i] < 0.0f), rh, t, i * Wd, 0);
+                }
+            }
+        } else if constexpr (FIX) {
             // n <= 2 VP T (see the LLR copy); rows through their descriptors as there: every LDS read
             // issued before the first store, a read past variable n - 1 takes the spare words and its
             // store is dropped.  wide_io: 16 bytes of posteriors and four packed decisions a store
@@ -1012,7 +1054,9 @@ hipError_t launch_loc_modes(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipS
     if (p.chain) {  // the chained layout: its tables, two row classes (pair slot 0 | the chained slots)
         if constexpr (ALGO == 0 && !ET && !MC) {
             constexpr int KP = kLocChainKP, T = kLocChainT;
-            if (g.chn_Tq <= 0 || g.chn_Tq > T || g.loc_P != KP * g.chn_Tq || !g.chn_var || !g.chn_pos)
+            // the kernel strides by the launch width and tests no lane: it must be Tq, and the rows 4 KP Tq long
+            if (g.chn_Tq <= 0 || g.chn_Tq > T || g.loc_P != KP * g.chn_Tq || !g.chn_var || !g.chn_pos ||
+                p.width != g.chn_Tq || a.n != 4 * KP * g.chn_Tq)
                 return hipErrorInvalidValue;
             a.loc_var = g.chn_var;
             a.loc_pos = g.chn_pos;
@@ -1024,7 +1068,7 @@ hipError_t launch_loc_modes(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipS
             a.loc_cls_w[0] = 0; a.loc_cls_w[1] = 8 * g.chn_Tq; a.loc_cls_w[2] = g.chn_words;
             a.loc_cls_d[0] = a.loc_cls_d[1] = 6;
             auto k = bp_loc_kernel<6, 6, 2, 2, KP, T, 0, false, false, false, false, false, kLocChainCL>;
-            return launch_lds(k, dim3(p.grid), dim3(T), p.lds, s, a);
+            return launch_lds(k, dim3(p.grid), dim3(p.width), p.lds, s, a);
         } else {
             return hipErrorInvalidValue;
         }

@@ -181,6 +181,7 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
         }
         default: return p;  // None (choose_path never gives an Ens* path: those are bp_ens_plan's)
     }
+    p.width = p.chain ? g.chn_Tq : p.threads;
     p.slab = slab_per_wg * (size_t)p.grid;
     p.scratch = p.slab;
     if (p.persistent) {

@@ -383,6 +383,25 @@ int ldpc_debug_bp_plan_io(const int32_t *check_ptr, const int32_t *check_var, co
     return LDPC_OK;
 }
 
+// The launch width (BpPlan::width: the threads a workgroup is launched with) of ldpc_debug_bp_plan's
+// calls, one per call: the chained layout's Tq for the call that takes it, else the plan's threads.
+int ldpc_debug_bp_plan_width(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                             const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
+                             int64_t *out) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out)) && cus > 0, "bad plan arguments");
+    HostGraph h;
+    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
+    GraphShape g;
+    HostLayouts L;
+    host_layouts(h, g, L, true, layout_options());
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 6 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        out[i] = bp_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus).width;
+    }
+    return LDPC_OK;
+}
+
 // The launch plans (bec_plan) of `count` BEC calls on an (n, m) graph of check degree dc (0:
 // irregular), from the shape alone.  calls[i] = {mode, B, iters, peel_cap}; out + 9 i = {kernel,
 // threads, W, plane bytes, codewords per workgroup, grid, LDS bytes, F, LDS cap}; names + 64 i:

@@ -287,6 +287,9 @@ struct BpPlan {
     BpPath path = BpPath::None;
     const char *name = "none";  // display name (ldpc_bp_kernel_name)
     int threads = 0, grid = 0;
+    // bp_plan: the threads a workgroup is launched with -- the chained layout's Tq (only its threads
+    // t < Tq own anything; `threads` stays its instantiation's T, the stride of its tables), else `threads`
+    int width = 0;
     size_t lds = 0;             // dynamic LDS bytes
     int lds_slots = 0;          // bp_generic_kernel / bp_ens_kernel <*,gmem>: message slots [0, lds_slots) kept in LDS
     bool chain = false;         // bp_loc_kernel: the chained layout's instantiation and tables

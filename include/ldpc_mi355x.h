@@ -789,6 +789,17 @@ int ldpc_debug_bp_plan_io(const int32_t *check_ptr, const int32_t *check_var, co
                           char *names);
 
 /*
+ * Host-only: the launch width of ldpc_debug_bp_plan's calls (same calls[i] int32[6]); out[i] int64 =
+ * the threads a workgroup is launched with.  The fixed-count sum-product call on a graph with a
+ * chained layout launches that layout's Tq threads (n / 20: only they own checks and variables;
+ * `threads` stays 512, its instantiation's shape and the stride of its tables); every other call
+ * launches the plan's `threads`.
+ */
+int ldpc_debug_bp_plan_width(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                             const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
+                             int64_t *out);
+
+/*
  * Host-only: the launch plans of `count` ensemble soft-decoding calls on the (n, dv, dc)
  * shape (csrc/bp_plan.cpp bp_ens_plan).  calls[i] = {B, iters, algo, early_stop, mc,
  * want_post}; out[i] int64[9] = {path, threads, grid, LDS bytes, lds_slots, 0, slab bytes, -1,
