@@ -76,6 +76,8 @@ SIGNATURES = {
     "ldpc_debug_bp_plan": ([P, P, P, P, i, i, i, P, i, P, P], i),
     "ldpc_debug_bp_plan_io": ([P, P, P, P, i, i, i, P, i, P, P], i),
     "ldpc_debug_bp_plan_width": ([P, P, P, P, i, i, i, P, i, P], i),
+    "ldpc_debug_bp_plan_tq": ([P, P, P, P, i, i, i, P, i, P], i),
+    "ldpc_debug_bp_decode_tq": ([P, i, P, i, i, P, P, P, P], i),
     "ldpc_bp_layered_decode_batch_dev": ([P, P, i, i, i, f, i, P, P, P, P], i),
     "ldpc_mc_layered_batch_dev": ([P, i, f, u64, u64, i, i, i, f, i, i, i64, P, P], i),
     "ldpc_debug_layer_schedule": ([P, P, P, P, i, i, P, P], i),

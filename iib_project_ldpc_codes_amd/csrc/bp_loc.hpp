@@ -50,9 +50,11 @@ __device__ __forceinline__ uint32_t bits_parity(const float2 (&x)[D], bool hi, u
 }
 // CL > 0 (the chained layout, bp_loc_kernel): input slot 2 is the thread's chain register *chain,
 // overwritten with that slot's output; the pair's rows hold the other D - 3 inputs.
+// The pair is entry off + i of its class: a caller that knows part of the index at compile time passes it as off,
+// and with W and Nc constants too every row access is one lane base (16 i or 8 i bytes) plus an immediate.
 template <int D, int ALGO, bool MIXED = false, bool SGN = false, int CL = 0>
 __device__ __forceinline__ int loc_check_pair(float *msg, int W, int Nc, int i, float2 &l0, float2 &l1, float alpha,
-                                              uint32_t lpar = 0u, float2 *chain = nullptr) {
+                                              uint32_t lpar = 0u, float2 *chain = nullptr, int off = 0) {
     constexpr int C = CL > 0 ? 1 : 0, U = D - 2 - C;
     float2 x[D];
     x[0] = l0;
@@ -60,11 +62,11 @@ __device__ __forceinline__ int loc_check_pair(float *msg, int W, int Nc, int i, 
     if constexpr (C) x[2] = *chain;
 #pragma unroll
     for (int r = 0; r < U / 2; ++r) {
-        const float4 f = *reinterpret_cast<const float4 *>(msg + W + r * 4 * Nc + 4 * i);
+        const float4 f = *reinterpret_cast<const float4 *>(msg + W + r * 4 * Nc + 4 * off + 4 * i);
         x[2 + C + 2 * r] = make_float2(f.x, f.y);
         x[3 + C + 2 * r] = make_float2(f.z, f.w);
     }
-    if constexpr (U % 2) x[D - 1] = *reinterpret_cast<const float2 *>(msg + W + (U / 2) * 4 * Nc + 2 * i);
+    if constexpr (U % 2) x[D - 1] = *reinterpret_cast<const float2 *>(msg + W + (U / 2) * 4 * Nc + 2 * off + 2 * i);
     int unsat = 0;
     if constexpr (SGN) {  // raw parity words: the caller ORs them and tests bit 0 once
         // a mixed pair's .x check has D - 1 inputs: its pad slot holds the rule's output for the
@@ -98,9 +100,9 @@ __device__ __forceinline__ int loc_check_pair(float *msg, int W, int Nc, int i, 
     }
 #pragma unroll
     for (int r = 0; r < U / 2; ++r)
-        *reinterpret_cast<float4 *>(msg + W + r * 4 * Nc + 4 * i) =
+        *reinterpret_cast<float4 *>(msg + W + r * 4 * Nc + 4 * off + 4 * i) =
             make_float4(x[2 + C + 2 * r].x, x[2 + C + 2 * r].y, x[3 + C + 2 * r].x, x[3 + C + 2 * r].y);
-    if constexpr (U % 2) *reinterpret_cast<float2 *>(msg + W + (U / 2) * 4 * Nc + 2 * i) = x[D - 1];
+    if constexpr (U % 2) *reinterpret_cast<float2 *>(msg + W + (U / 2) * 4 * Nc + 2 * off + 2 * i) = x[D - 1];
     l0 = x[0];
     l1 = x[1];
     if constexpr (C) *chain = x[2];
@@ -198,9 +200,13 @@ constexpr int loc_waves_per_simd(int T, int KP) { return T == 512 && KP <= 5 ? 4
 // chain[k - 1] and has three LDS inputs (class 1: rows of (KP - 1) Tq pairs from word
 // a.loc_cls_w[1]); var pair 2k + 1, k < CL, has one LDS edge (row 0 of loc_pos) and chain[k].
 // Fixed-count sum-product only.
+// TQ > 0 (a row of LDPC_LOC_CHAIN_TQ, kernel_shapes.hpp): that Tq as a compile-time constant -- n = 4 KP TQ, the
+// class-1 word base, the class sizes and the copies' strides fold, and the check phase's row offsets are
+// instruction immediates.  The launcher starts it only on a plan of that width.
 template <int DLO, int DHI, int DVN0, int DVN1, int KP, int T, int ALGO, bool ABS0, bool ABS1, bool ET = false,
-          bool MC = false, bool EP = false, int CL = 0>
+          bool MC = false, bool EP = false, int CL = 0, int TQ = 0>
 __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(BpArgs a) {
+    static_assert(TQ == 0 || (CL > 0 && TQ <= T), "a compile-time width: the chained layout only");
     static_assert(CL == 0 || (CL == KP - 1 && ALGO == 0 && !ET && !MC && !EP && DLO == DHI && DVN1 == 2 && !ABS1),
                   "chained layout: fixed-count sum-product on the one-class shape");
     // var pair v's last non-local edge is the chain register chain[v / 2]
@@ -222,12 +228,12 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
     __shared__ uint32_t stop_flag[2];  // early stop: block_any's double-buffered flag
     float *msg = reinterpret_cast<float *>(smem);
     const int tid = threadIdx.x;
-    const int n = a.n, iters = a.max_iters;
+    const int n = TQ > 0 ? 4 * KP * TQ : a.n, iters = a.max_iters;
     // the launch width: the chained instantiation runs Tq threads (launch_loc_modes), each with all
     // KP pair slots and its 4 KP variables -- no lane of it tests tid < Tq, a part-filled last wave
     // is the hardware's EXEC mask, and what the workgroup does together strides by Wd.  T stays
     // the stride of the thread-layout tables.
-    const int Wd = CL > 0 ? a.loc_cls_q[1] : T;
+    const int Wd = TQ > 0 ? TQ : CL > 0 ? a.loc_cls_q[1] : T;
     const int lpos0 = (int)((uint32_t)(size_t)(lds_u8 *)smem >> 2);
     const uint32_t base2 = (uint32_t)lpos0 | ((uint32_t)lpos0 << 16);
     constexpr bool SPA = ALGO == 0;
@@ -651,15 +657,27 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
                 // every thread of the launch owns all KP pair slots: no lane test around the phase
                 // (one would cost the loop a register copy per value it rewrites, at the join)
                 const int Tq = Wd;
+                // class 1's rows start behind class 0's two float4 rows of Tq pairs (build_loc_chain_layout:
+                // word 8 Tq; the launcher passes the same as a.loc_cls_w[1])
+                const int W1 = TQ > 0 ? 8 * TQ : a.loc_cls_w[1];
+                // TQ: the last row access, slot KP - 1's float2 row, is the immediate 4 (W1 + 16 Tq + 2 (KP - 2) Tq)
+                // = 120 Tq bytes behind its lane base, within a ds_* instruction's 16-bit offset (64: room for
+                // the kernel's static LDS, 16 bytes, which the compiler folds into the same immediate)
+                static_assert(4 * (8 * TQ + 4 * (KP - 1) * TQ + 2 * (KP - 2) * TQ) + 64 <= 65535,
+                              "the chained rows' offsets are instruction immediates");
 #pragma unroll
                 for (int k = 0; k < KP; ++k) {
-                    int i = tid + (k > 0 ? (k - 1) * Tq : 0);  // index in the pair's class
-                    asm volatile("" : "+v"(i));  // recomputed per iteration, as q below
+                    // the pair is entry i + off of its class.  TQ: the slot's part is a constant, so every row of
+                    // the phase is a lane base (16 tid or 8 tid bytes, loop-invariant and held in a register
+                    // each) plus an immediate; else the index is recomputed per iteration, as q below
+                    const int off = TQ > 0 && k > 0 ? (k - 1) * TQ : 0;
+                    int i = TQ > 0 ? tid : tid + (k > 0 ? (k - 1) * Tq : 0);
+                    if constexpr (TQ == 0) asm volatile("" : "+v"(i));
                     if (k == 0)
                         loc_check_pair<DLO, ALGO>(msg, 0, Tq, i, loc[0], loc[1], a.alpha);
                     else
-                        loc_check_pair<DLO, ALGO, false, false, CL>(msg, a.loc_cls_w[1], (KP - 1) * Tq, i, loc[2 * k],
-                                                                    loc[2 * k + 1], a.alpha, 0u, &chain[k - 1]);
+                        loc_check_pair<DLO, ALGO, false, false, CL>(msg, W1, (KP - 1) * Tq, i, loc[2 * k],
+                                                                    loc[2 * k + 1], a.alpha, 0u, &chain[k - 1], off);
                     if (LDPC_LOC_CGROUP > 0 && k % LDPC_LOC_CGROUP == LDPC_LOC_CGROUP - 1)
                         __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1067,6 +1085,18 @@ hipError_t launch_loc_modes(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipS
             a.loc_cls_q[0] = 0; a.loc_cls_q[1] = g.chn_Tq; a.loc_cls_q[2] = g.loc_P;
             a.loc_cls_w[0] = 0; a.loc_cls_w[1] = 8 * g.chn_Tq; a.loc_cls_w[2] = g.chn_words;
             a.loc_cls_d[0] = a.loc_cls_d[1] = 6;
+            // a plan with a compile-time width (BpPlan::tq): that row's instantiation, which takes Tq, n and the
+            // class table from its template argument -- started on no other width
+            if (p.tq != 0) {
+                if (p.tq != g.chn_Tq) return hipErrorInvalidValue;
+#define LDPC_ROW(TQ)                                                                                           \
+    if (p.tq == TQ)                                                                                            \
+        return launch_lds(bp_loc_kernel<6, 6, 2, 2, KP, T, 0, false, false, false, false, false, kLocChainCL, TQ>, \
+                          dim3(p.grid), dim3(p.width), p.lds, s, a);
+                LDPC_LOC_CHAIN_TQ(LDPC_ROW)
+#undef LDPC_ROW
+                return hipErrorInvalidValue;
+            }
             auto k = bp_loc_kernel<6, 6, 2, 2, KP, T, 0, false, false, false, false, false, kLocChainCL>;
             return launch_lds(k, dim3(p.grid), dim3(p.width), p.lds, s, a);
         } else {

@@ -182,6 +182,10 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
         default: return p;  // None (choose_path never gives an Ens* path: those are bp_ens_plan's)
     }
     p.width = p.chain ? g.chn_Tq : p.threads;
+    // the chained call at a width that has an instantiation of its own
+    if (p.chain && g.chn_tq)
+        for (int tq : shapes::kLocChainTq)
+            if (tq == g.chn_Tq) p.tq = tq;
     p.slab = slab_per_wg * (size_t)p.grid;
     p.scratch = p.slab;
     if (p.persistent) {

@@ -26,7 +26,8 @@ DropInCache g_dropin;
 
 // The layout environment, read here and nowhere else: LDPC_NO_LOC_LAYOUT=1 builds no local-edge
 // layout (tests run the other kernels on the same graphs), LDPC_NO_LOC_CHAIN=1 no chained layout
-// beside it (fixed-count sum-product decodes then run on the plain one), LDPC_LOC_T sets its thread count
+// beside it (fixed-count sum-product decodes then run on the plain one), LDPC_NO_LOC_TQ=1 keeps the chained
+// layout on the generic instantiation at every width (tests hold the width's own to it), LDPC_LOC_T sets its thread count
 // (shape experiments); an explicit loc_T (ldpc_debug_loc_variant) goes over the environment's.
 // LDPC_NO_QC_KERNEL=1 keeps a quasi-cyclic graph's block-row schedule but not its row table
 // (qc_Z = 0): it decodes on the table kernels (tests and A/B runs hold bp_qc_q_kernel to them).
@@ -36,6 +37,8 @@ LayoutOptions layout_options(int loc_T = 0) {
     opt.loc_layout = !(noloc && noloc[0] == '1');
     const char *nochain = getenv("LDPC_NO_LOC_CHAIN");
     opt.loc_chain = !(nochain && nochain[0] == '1');
+    const char *notq = getenv("LDPC_NO_LOC_TQ");
+    opt.loc_tq = !(notq && notq[0] == '1');
     if (const char *t = getenv("LDPC_LOC_T")) opt.loc_T = atoi(t);
     if (loc_T) opt.loc_T = loc_T;
     const char *noqc = getenv("LDPC_NO_QC_KERNEL");
@@ -399,6 +402,43 @@ int ldpc_debug_bp_plan_width(const int32_t *check_ptr, const int32_t *check_var,
         LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
         out[i] = bp_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus).width;
     }
+    return LDPC_OK;
+}
+
+// The compile-time width (BpPlan::tq) of the same calls, one per call: the chained call's Tq where
+// LDPC_LOC_CHAIN_TQ lists it and LDPC_NO_LOC_TQ is not set, else 0 (the generic instantiation, every other kernel).
+int ldpc_debug_bp_plan_tq(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                          const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
+                          int64_t *out) {
+    LDPC_REQUIRE(count >= 0 && (count == 0 || (calls && out)) && cus > 0, "bad plan arguments");
+    HostGraph h;
+    LDPC_TRY(host_graph_from_csr(check_ptr, check_var, var_ptr, var_slot, n, m, h));
+    GraphShape g;
+    HostLayouts L;
+    host_layouts(h, g, L, true, layout_options());
+    for (int i = 0; i < count; ++i) {
+        const int32_t *c = calls + 6 * (size_t)i;
+        LDPC_REQUIRE(c[0] >= 0 && c[1] >= 0, "bad plan arguments");
+        out[i] = bp_plan(g, c[0], c[1], c[2], c[3] != 0, c[4] != 0, c[5] != 0, cus).tq;
+    }
+    return LDPC_OK;
+}
+
+// ldpc_bp_decode_batch_dev's fixed-count sum-product decode from its own plan but for BpPlan::tq, which is `tq`:
+// what the launcher answers to a plan whose compile-time width is not the graph's (LDPC_EHIP, nothing started).
+int ldpc_debug_bp_decode_tq(const ldpc_graph *g, int tq, const float *d_llr, int B, int max_iters, float *d_post,
+                            uint8_t *d_hard, int32_t *d_its, void *stream) {
+    LDPC_REQUIRE(g && d_llr && B > 0 && max_iters >= 0 && tq >= 0, "bad soft batch arguments");
+    LDPC_REQUIRE(g->consistent, "soft decoding needs consistent edge lists");
+    const SoftCall c = decode_call(B, max_iters, LDPC_ALGO_SPA, 1.0f, 0, d_llr, d_post, d_hard, d_its);
+    const FloodFamily f{*g};
+    std::lock_guard<std::mutex> lk(g_mu);
+    Workspace &ws = workspace(stream);
+    std::lock_guard<std::mutex> wl(ws.mu);
+    BpPlan p = f.plan(c, device_cus());
+    LDPC_REQUIRE(p.path == BpPath::Loc && p.chain && p.scratch == 0, "not a chained-layout call");
+    p.tq = tq;
+    LDPC_HIP(f.launch(p, c, nullptr, static_cast<hipStream_t>(stream)));
     return LDPC_OK;
 }
 

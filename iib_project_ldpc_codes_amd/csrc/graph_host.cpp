@@ -476,6 +476,7 @@ void host_layouts(const HostGraph &h, GraphShape &g, HostLayouts &L, bool layout
                 build_loc_chain_layout(h.n, h.m, h.cptr, h.cvar, h.vptr, h.vslot, K, L.chain)) {
                 g.chn_Tq = L.chain.Tq;
                 g.chn_words = L.chain.words;
+                g.chn_tq = opt.loc_tq;
             } else {
                 L.chain = LocChainLayout();
             }

@@ -68,6 +68,7 @@ struct LayoutOptions {
     bool loc_layout = true;  // build the local-edge layout (off: tests run the other kernels on the same graphs)
     int loc_T = 0;           // threads of the local-edge layout, 0 = the shipped choice
     bool loc_chain = true;   // build the chained layout beside it (off: tests and A/B runs of the plain one)
+    bool loc_tq = true;      // ... decoded by the instantiation of its width where there is one (off: the generic one)
     const QcCode *qc = nullptr;  // the graph is this quasi-cyclic code's expansion: its block rows are the layers
     bool qc_kernel = true;       // ... and it runs bp_qc_q_kernel (off: the table kernels on the block-row schedule)
 };

@@ -32,6 +32,10 @@
 #define LDPC_LOC_SHAPES(X) X(256, 1) X(256, 2) X(256, 3) X(256, 4) X(1024, 2) X(1024, 3)
 #define LDPC_LOC_REG36_SHAPES(X) X(512, 5)
 #define LDPC_LOC_RSU_SHAPES(X) X(512, 8) X(512, 10)
+// bp_loc_kernel<..., CL, TQ> (bp_loc.hpp): the widths Tq = n / 20 of the chained layout that have an instantiation
+// of their own, with Tq a compile-time constant.  500: n = 10,000, the benchmark's code.  A width is added for a
+// code that is decoded for long (each row is another 128-VGPR kernel to compile); every other Tq runs the generic one.
+#define LDPC_LOC_CHAIN_TQ(X) X(500)
 // sample_regular_kernel (sampler.hip): buckets (= threads), permutation entry, its tag, the
 // permutation in LDS, that as a tag
 #define LDPC_SAMPLE_LEVEL_SHAPES(X) \
@@ -80,6 +84,9 @@ constexpr EncTile kEncTiles[] = {LDPC_ENC_TILES(LDPC_ROW)};
 constexpr Shape2 kLds36[] = {LDPC_LDS36_SHAPES(LDPC_ROW)};
 constexpr Shape2 kLocReg36[] = {LDPC_LOC_SHAPES(LDPC_ROW) LDPC_LOC_REG36_SHAPES(LDPC_ROW)};
 constexpr Shape2 kLocRsu[] = {LDPC_LOC_SHAPES(LDPC_ROW) LDPC_LOC_RSU_SHAPES(LDPC_ROW)};
+#undef LDPC_ROW
+#define LDPC_ROW(TQ) TQ,
+constexpr int kLocChainTq[] = {LDPC_LOC_CHAIN_TQ(LDPC_ROW)};
 #undef LDPC_ROW
 #define LDPC_ROW(K, IDX, TAG, LDSBUF, MEM) {K, LDSBUF, "sample_regular_kernel<" #K "," #TAG "," #MEM ">"},
 constexpr SampleLevel kSampleLevel[] = {LDPC_SAMPLE_LEVEL_SHAPES(LDPC_ROW)};

@@ -41,6 +41,9 @@ struct GraphShape {
     // Chained local-edge layout beside it (build_loc_chain_layout; fixed-count sum-product
     // decodes run on it); chn_Tq == 0: none
     int chn_Tq = 0, chn_words = 0;
+    // ... on the instantiation with that Tq as a constant where kernel_shapes.hpp lists one (false:
+    // LDPC_NO_LOC_TQ=1, the generic instantiation at every width)
+    bool chn_tq = true;
     // Layer schedule of bp_layer_kernel (build_layer_schedule, graph_host.cpp): lay_L layers, the
     // largest of lay_max checks; lay_L == 0: none
     int lay_L = 0, lay_max = 0;
@@ -290,7 +293,10 @@ struct BpPlan {
     // bp_plan: the threads a workgroup is launched with -- the chained layout's Tq (only its threads
     // t < Tq own anything; `threads` stays its instantiation's T, the stride of its tables), else `threads`
     int width = 0;
-    size_t lds = 0;             // dynamic LDS bytes
+    // bp_plan: the chained call's compile-time width -- `width` when LDPC_LOC_CHAIN_TQ (kernel_shapes.hpp) lists it,
+    // the instantiation bp_loc_kernel<..., CL, tq>; 0: the generic instantiation, and every other call
+    int tq = 0;
+    size_t lds = 0;            // dynamic LDS bytes
     int lds_slots = 0;          // bp_generic_kernel / bp_ens_kernel <*,gmem>: message slots [0, lds_slots) kept in LDS
     bool chain = false;         // bp_loc_kernel: the chained layout's instantiation and tables
     bool wide_io = false;       // bp_loc_kernel, fixed count: 16-byte row I/O (bp_wide_io; FloodFamily::plan sets it)

@@ -800,6 +800,25 @@ int ldpc_debug_bp_plan_width(const int32_t *check_ptr, const int32_t *check_var,
                              int64_t *out);
 
 /*
+ * Host-only: the compile-time width of the same calls; out[i] int64 = Tq when the call is the
+ * fixed-count sum-product decode on a chained layout whose Tq has an instantiation of its own
+ * (bp_loc_kernel with Tq a template argument: 500, n = 10,000), 0 for every other call and width,
+ * and for every call under LDPC_NO_LOC_TQ=1 (read when the graph's layouts are built).
+ */
+int ldpc_debug_bp_plan_tq(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,
+                          const int32_t *var_slot, int n, int m, int count, const int32_t *calls, int cus,
+                          int64_t *out);
+
+/*
+ * Test entry: ldpc_bp_decode_batch_dev's fixed-count sum-product decode (B > 0) on a graph with a
+ * chained layout, launched from its own plan with the plan's compile-time width replaced by tq.
+ * tq = 0 runs the generic instantiation; a tq that is not the graph's Tq is refused by the
+ * launcher: LDPC_EHIP, and no kernel is started.
+ */
+int ldpc_debug_bp_decode_tq(const ldpc_graph *g, int tq, const float *d_llr, int B, int max_iters, float *d_post,
+                            uint8_t *d_hard, int32_t *d_its, void *stream);
+
+/*
  * Host-only: the launch plans of `count` ensemble soft-decoding calls on the (n, dv, dc)
  * shape (csrc/bp_plan.cpp bp_ens_plan).  calls[i] = {B, iters, algo, early_stop, mc,
  * want_post}; out[i] int64[9] = {path, threads, grid, LDS bytes, lds_slots, 0, slab bytes, -1,

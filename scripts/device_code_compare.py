@@ -9,7 +9,8 @@ extracted with `git archive` into a temporary directory) and once from the worki
 is normalised, cut into kernels, and each kernel instantiation is reduced to an instruction count,
 a digest and its resources.  A kernel's own symbol is written <self> in its text, so an instantiation
 whose mangled name alone changed (a template parameter pack added behind the others, empty for it)
-compares equal under its demangled name.  An instantiation the parent does not have is listed as
+compares equal under its demangled name; --defaulted-arg VALUE does the same for a template argument added
+behind the others with a default.  An instantiation the parent does not have is listed as
 added ("identical": null) and is no difference.  Needs hipcc and git, no GPU.  Exit status 1 when
 anything differs.
 """
@@ -106,6 +107,9 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--what", default=None)
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--defaulted-arg", default=None, metavar="VALUE",
+                    help="a template argument added behind the others with this default: an instantiation that ends "
+                         "', VALUE>' and that the parent lacks is compared with the parent's of the name without it")
     ap.add_argument("files", nargs="*")
     a = ap.parse_args()
     files = a.files or default_files()
@@ -119,6 +123,10 @@ def main():
     rows = []
     for f in files:
         old, new = kernels(texts[(parent, f)]), kernels(texts[(ROOT, f)])
+        if a.defaulted_arg is not None:  # the parent's instantiations under the names they have now
+            tail = ", %s>(" % a.defaulted_arg
+            was = {k.replace(tail, ">(", 1): k for k in new if k not in old and tail in k}
+            old = {was.get(k, k): v for k, v in old.items()}
         for k in sorted(set(old) | set(new)):
             rows.append({"file": f, "kernel": k, "parent": old.get(k), "new": new.get(k),
                          "identical": old[k] == new.get(k) if k in old else None})
