@@ -2,17 +2,11 @@
 // Included by bp_loc_spa.hip and bp_loc_ms.hip, which instantiate one algorithm each (the
 // kernel's instantiations are most of the library's compile time).
 #pragma once
-#include "bp_device.hpp"
+#include "bp_loc_common.hpp"
 
 namespace ldpc {
 namespace {
 
-#ifndef LDPC_LOC_VGROUP
-#define LDPC_LOC_VGROUP 1  // bp_loc_kernel: variable pairs per scheduling group (0: no barriers)
-#endif
-#ifndef LDPC_LOC_CGROUP
-#define LDPC_LOC_CGROUP 1  // bp_loc_kernel: check pairs per scheduling group (0: no barriers)
-#endif
 // ---------------------------------------------------------------------------
 // 2a'. Local-edge kernel (layout: loc_layout.cpp).  One codeword per workgroup of T
 //   threads; thread t updates check pairs q = t + kT (k < KP) and the four variables
@@ -29,85 +23,6 @@ namespace {
 //   ABS: some variables have fewer than DVN+1 edges; their absent edges gather the
 //   neutral value (ratio 1 / sum 0) and write to a private dummy word.
 // ---------------------------------------------------------------------------
-// SGN (sum-product with early stop): every non-local v->c ratio carries its variable's hard
-// decision in one bit; with the decisions of the pair's two local variables (lpar, from the
-// thread's own decision bits: bit 0 the .x check's, bit 1 the .y check's parity of them) the
-// pair's parities are the syndrome of the previous variable phase (returned: 1 = a check of
-// the pair unsatisfied).  The bit is the ratio's mantissa LSB (a relative change of at most
-// 2^-23, far below the rule's ~10-ulp error), so the check rule takes the inputs as they are:
-// the parity is two v_bitop3 XOR chains and one OR per pair, no input needs its sign stripped,
-// and the local edges (registers) carry no stamp.
-// seed ^ the words of entries 2 .. N-1 (N <= D) of one half of x
-template <int N, int D>
-__device__ __forceinline__ uint32_t bits_parity(const float2 (&x)[D], bool hi, uint32_t seed) {
-    auto w = [&](int j) { return __float_as_uint(hi ? x[j].y : x[j].x); };
-    uint32_t p = seed;
-    int j = 2;
-#pragma unroll
-    for (; j + 1 < N; j += 2) p = xor3u(p, w(j), w(j + 1));
-    if (j < N) p ^= w(j);
-    return p;
-}
-// CL > 0 (the chained layout, bp_loc_kernel): input slot 2 is the thread's chain register *chain,
-// overwritten with that slot's output; the pair's rows hold the other D - 3 inputs.
-// The pair is entry off + i of its class: a caller that knows part of the index at compile time passes it as off,
-// and with W and Nc constants too every row access is one lane base (16 i or 8 i bytes) plus an immediate.
-template <int D, int ALGO, bool MIXED = false, bool SGN = false, int CL = 0>
-__device__ __forceinline__ int loc_check_pair(float *msg, int W, int Nc, int i, float2 &l0, float2 &l1, float alpha,
-                                              uint32_t lpar = 0u, float2 *chain = nullptr, int off = 0) {
-    constexpr int C = CL > 0 ? 1 : 0, U = D - 2 - C;
-    float2 x[D];
-    x[0] = l0;
-    x[1] = l1;
-    if constexpr (C) x[2] = *chain;
-#pragma unroll
-    for (int r = 0; r < U / 2; ++r) {
-        const float4 f = *reinterpret_cast<const float4 *>(msg + W + r * 4 * Nc + 4 * off + 4 * i);
-        x[2 + C + 2 * r] = make_float2(f.x, f.y);
-        x[3 + C + 2 * r] = make_float2(f.z, f.w);
-    }
-    if constexpr (U % 2) x[D - 1] = *reinterpret_cast<const float2 *>(msg + W + (U / 2) * 4 * Nc + 2 * off + 2 * i);
-    int unsat = 0;
-    if constexpr (SGN) {  // raw parity words: the caller ORs them and tests bit 0 once
-        // a mixed pair's .x check has D - 1 inputs: its pad slot holds the rule's output for the
-        // padding input (an arbitrary LSB), not a variable's decision
-        unsat = (int)(bits_parity<MIXED ? D - 1 : D, D>(x, false, lpar) | bits_parity<D, D>(x, true, lpar >> 1));
-    }
-    if constexpr (ALGO == 0) {
-        if constexpr (MIXED) {  // the .x check has D - 1 edges: pad input R = 0
-            x[D - 1].x = 0.0f;
-            check_update_spa_pair_rwire<D, true>(x);
-        } else {
-            check_update_spa_pair_rwire<D>(x);
-        }
-    } else {
-        float xa[D], xb[D];
-#pragma unroll
-        for (int j = 0; j < D; ++j) { xa[j] = x[j].x; xb[j] = x[j].y; }
-        if constexpr (MIXED) {  // pad: an infinite magnitude changes no minimum or sign
-            xa[D - 1] = __builtin_inff();
-            check_update<1, D>(xa, alpha);
-            check_update<1, D>(xb, alpha);
-        } else if constexpr (D == 6) {
-            check_update_ms6(xa, alpha);
-            check_update_ms6(xb, alpha);
-        } else {
-            check_update<1, D>(xa, alpha);
-            check_update<1, D>(xb, alpha);
-        }
-#pragma unroll
-        for (int j = 0; j < D; ++j) x[j] = make_float2(xa[j], xb[j]);
-    }
-#pragma unroll
-    for (int r = 0; r < U / 2; ++r)
-        *reinterpret_cast<float4 *>(msg + W + r * 4 * Nc + 4 * off + 4 * i) =
-            make_float4(x[2 + C + 2 * r].x, x[2 + C + 2 * r].y, x[3 + C + 2 * r].x, x[3 + C + 2 * r].y);
-    if constexpr (U % 2) *reinterpret_cast<float2 *>(msg + W + (U / 2) * 4 * Nc + 2 * off + 2 * i) = x[D - 1];
-    l0 = x[0];
-    l1 = x[1];
-    if constexpr (C) *chain = x[2];
-    return unsat;
-}
 
 // code = dy, or dy | dx << 8 for a mixed pair (dx = dy - 1 = DHI - 1 only)
 template <int D, int DHI, int ALGO, bool SGN>
@@ -122,67 +37,6 @@ __device__ __forceinline__ int loc_check_dispatch(int code, float *msg, int W, i
     }
 }
 
-// a load whose index the compiler may not hoist out of the codeword loop (it would keep
-// one 64-bit address per load live across the decode -- VGPRs the loop needs)
-template <typename V>
-__device__ __forceinline__ V ld_fresh(const V *p, int idx) {
-    asm volatile("" : "+v"(idx));
-    return p[idx];
-}
-// Row b of a [B][len] tensor as a raw buffer of `bytes` bytes: stride 0, no swizzle, and in the
-// descriptor's last word only DATA_FORMAT (bits 18:15) = 4, a 32-bit element -- a zero there is the
-// invalid format of an unbound resource; the untyped loads and stores below read no other field of
-// it.  Base = the row start (a 64-bit scalar add: a batch past 4 GB stays clear of the 32-bit lane
-// offsets).  The hardware's range check (offset >= bytes) returns 0 from a load past the row and
-// drops a store past it, so no access below carries a guard of its own; every access is aligned to
-// its own size and len % 4 = 0, so none straddles the row's end
-// (tests/test_gpu_loc_row_io.py holds this with sentinels around every output row).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void *row, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(row), 0, bytes, 0x00020000);
-}
-// Entry `entry` (a compile-time constant: the row's start) + lane of a thread-layout table of int32
-// through the table's descriptor: the row's byte offset is the instruction's scalar offset, the
-// lane's part one 32-bit byte offset (lane_bytes = 4 tid, made opaque where it is formed, so -- as
-// with ld_fresh -- nothing per entry is held across the decode, and no 64-bit VALU address is formed)
-__device__ __forceinline__ int32_t ld_row(__amdgpu_buffer_rsrc_t tab, int entry, uint32_t lane_bytes) {
-    return (int32_t)__builtin_amdgcn_raw_buffer_load_b32(tab, lane_bytes, 4 * entry, 0);
-}
-
-// Workgroup-wide OR of a per-lane predicate with ONE barrier (__syncthreads_or reduces
-// through a wave DPP chain, an LDS atomic and three barriers): each wave whose ballot is
-// non-zero has lane 0 store 1 to flag[par]; after the barrier every thread reads it; thread 0
-// then clears flag[par ^ 1] -- its previous readers are all past this barrier, and its next
-// writers are behind the next one.  flag[] must be zero before the first call; alternate par.
-__device__ __forceinline__ bool block_any(int pred, uint32_t *flag, int par) {
-    if (__builtin_amdgcn_ballot_w64(pred != 0) != 0 && (threadIdx.x & (kWave - 1)) == 0) flag[par] = 1u;
-    __syncthreads();
-    const bool any = flag[par] != 0u;
-    if (threadIdx.x == 0) flag[par ^ 1] = 0u;
-    return any;
-}
-// block_any's count form: the number of waves' lanes with pred set (one LDS atomic per wave)
-__device__ __forceinline__ uint32_t block_count(int pred, uint32_t *flag, int par) {
-    const uint64_t bal = __builtin_amdgcn_ballot_w64(pred != 0);
-    if (bal != 0 && (threadIdx.x & (kWave - 1)) == 0) atomicAdd(&flag[par], (uint32_t)__popcll(bal));
-    __syncthreads();
-    const uint32_t c = flag[par];
-    if (threadIdx.x == 0) flag[par ^ 1] = 0u;
-    return c;
-}
-#ifndef LDPC_LOC_EP_W0
-#define LDPC_LOC_EP_W0 48  // early stop with posteriors: slab writes after syndromes with <= this many threads unsatisfied
-#endif
-#ifndef LDPC_LOC_PRIO
-// wave priority by phase: the variable phase (LDS-bound gathers / scatters) at s_setprio 1, the
-// check phase (VALU-bound) at 0 -- two co-resident workgroups in opposite phases then share the
-// SIMD in favour of the one that feeds the LDS pipe.  Headline +1.9 % (28.94 -> 28.39 ms), early
-// stop and Monte-Carlo +1-3 %; the reverse assignment -2.4 %, odd workgroups at 1 neutral.
-#define LDPC_LOC_PRIO 1
-#endif
-
-
 // DVN0 / DVN1: non-local edges per variable of local slot 0 / 1 (max); ABS0 / ABS1: some
 // variable of that slot has fewer (its absent edges gather the neutral value).
 // MC (sum-product): fused Philox channel, per-iteration error counts of the all-zero
@@ -191,27 +45,9 @@ __device__ __forceinline__ uint32_t block_count(int pred, uint32_t *flag, int pa
 // asked for no posteriors): the same stop, the decisions of the stopping iteration kept in a
 // bit per variable (hbits) and written out; a frame that never stops takes the fixed-count
 // epilogue.
-// 512 threads with up to 5 check pairs each: two workgroups per CU (4 waves per SIMD, <= 128
-// VGPRs), so one workgroup's barrier waits overlap the other's work; else one workgroup
-constexpr int loc_waves_per_simd(int T, int KP) { return T == 512 && KP <= 5 ? 4 : 1; }
-
-// CL > 0: the chained layout (loc_layout.cpp) with CL = KP - 1 chain links per thread, launched
-// Tq (a.loc_cls_q[1]) threads wide: thread t owns pairs t + k Tq; pair slot k >= 1 takes its input slot 2 from
-// chain[k - 1] and has three LDS inputs (class 1: rows of (KP - 1) Tq pairs from word
-// a.loc_cls_w[1]); var pair 2k + 1, k < CL, has one LDS edge (row 0 of loc_pos) and chain[k].
-// Fixed-count sum-product only.
-// TQ > 0 (a row of LDPC_LOC_CHAIN_TQ, kernel_shapes.hpp): that Tq as a compile-time constant -- n = 4 KP TQ, the
-// class-1 word base, the class sizes and the copies' strides fold, and the check phase's row offsets are
-// instruction immediates.  The launcher starts it only on a plan of that width.
 template <int DLO, int DHI, int DVN0, int DVN1, int KP, int T, int ALGO, bool ABS0, bool ABS1, bool ET = false,
-          bool MC = false, bool EP = false, int CL = 0, int TQ = 0>
+          bool MC = false, bool EP = false>
 __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(BpArgs a) {
-    static_assert(TQ == 0 || (CL > 0 && TQ <= T), "a compile-time width: the chained layout only");
-    static_assert(CL == 0 || (CL == KP - 1 && ALGO == 0 && !ET && !MC && !EP && DLO == DHI && DVN1 == 2 && !ABS1),
-                  "chained layout: fixed-count sum-product on the one-class shape");
-    // var pair v's last non-local edge is the chain register chain[v / 2]
-    auto chained = [](int v) { return CL > 0 && (v & 1) && (v >> 1) < CL; };
-    float2 chain[CL > 0 ? CL : 1];
     static_assert(!ET || ALGO == 0 || DLO == DHI, "min-sum early stop: one check class");
     static_assert(!ET || 2 * 2 * KP <= 64, "early stop keeps the thread's decisions in one 64-bit word");
     // MSET (min-sum Monte-Carlo with early stop): min-sum messages carry their own signs, so
@@ -228,12 +64,7 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
     __shared__ uint32_t stop_flag[2];  // early stop: block_any's double-buffered flag
     float *msg = reinterpret_cast<float *>(smem);
     const int tid = threadIdx.x;
-    const int n = TQ > 0 ? 4 * KP * TQ : a.n, iters = a.max_iters;
-    // the launch width: the chained instantiation runs Tq threads (launch_loc_modes), each with all
-    // KP pair slots and its 4 KP variables -- no lane of it tests tid < Tq, a part-filled last wave
-    // is the hardware's EXEC mask, and what the workgroup does together strides by Wd.  T stays
-    // the stride of the thread-layout tables.
-    const int Wd = TQ > 0 ? TQ : CL > 0 ? a.loc_cls_q[1] : T;
+    const int n = a.n, iters = a.max_iters;
     const int lpos0 = (int)((uint32_t)(size_t)(lds_u8 *)smem >> 2);
     const uint32_t base2 = (uint32_t)lpos0 | ((uint32_t)lpos0 << 16);
     constexpr bool SPA = ALGO == 0;
@@ -249,10 +80,7 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         asm volatile("" : "+v"(l));
         return l;
     };
-    auto load_sp = [&](int v, int u, uint32_t lane4 = 0u) {
-        if constexpr (CL > 0) return (uint32_t)ld_row(row_rsrc(a.loc_pos, VP * DVP * T * 4), (v * DVP + u) * T, lane4) + base2;
-        else return (uint32_t)ld_fresh(a.loc_pos, (v * DVP + u) * T + tid) + base2;
-    };
+    auto load_sp = [&](int v, int u) { return (uint32_t)ld_fresh(a.loc_pos, (v * DVP + u) * T + tid) + base2; };
     // the variable ids of the thread's var pairs (entry 2v + h; -1: none), every load issued
     // before the first use (one L2 round trip, not one per var pair; Monte-Carlo staging)
     auto load_vars = [&](int (&vv)[2 * VP]) {
@@ -272,22 +100,17 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
     const float neutral = SPA ? 1.0f : 0.0f;
 
     // gather the non-local c->v messages of var pair v (slot s) into cv[0 .. DN-1]
-    // (a chained var pair's last edge comes from its chain register)
     auto gather = [&](auto dn_tag, auto abs_tag, int v, const uint32_t (&spv)[DVA], float2 (&cv)[DVA],
                       uint32_t (&a0)[DVA], uint32_t (&a1)[DVA]) {
         constexpr int DN = decltype(dn_tag)::value;
         constexpr bool AB = decltype(abs_tag)::value;
-        const int nl = chained(v) ? DN - 1 : DN;
 #pragma unroll
-        for (int u = 0; u < DN; ++u)
-            if (u < nl) {
-                a0[u] = pos_lo_x4(spv[u]);
-                a1[u] = pos_hi_x4(spv[u]);
-            }
+        for (int u = 0; u < DN; ++u) {
+            a0[u] = pos_lo_x4(spv[u]);
+            a1[u] = pos_hi_x4(spv[u]);
+        }
 #pragma unroll
-        for (int u = 0; u < DN; ++u)
-            if (u < nl) cv[u] = make_float2(at(a0[u]), at(a1[u]));
-        if (chained(v)) cv[DN - 1] = chain[v >> 1];
+        for (int u = 0; u < DN; ++u) cv[u] = make_float2(at(a0[u]), at(a1[u]));
         if constexpr (AB) {
 #pragma unroll
             for (int u = 0; u < DN; ++u) {
@@ -429,25 +252,17 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         if constexpr (ET) {
             if (tid == 0) stop_flag[0] = stop_flag[1] = 0u;  // visible after the staging barrier
         }
-        // the chained layout's decodes issue every table load (L2) before the LLR copy (HBM), so
-        // the two latencies overlap; the others load after it (batched there: neutral to 0.5 % slower)
-        constexpr bool STG = CL > 0;
+        // the table loads follow the LLR copy (batched before it: neutral to 0.5 % slower)
         auto load_tabs = [&]() {
-            const uint32_t lane4 = CL > 0 ? lane_bytes() : 0u;
 #pragma unroll
             for (int k = 0; k < KP; ++k) {
 #pragma unroll
-                for (int u = 0; u < DVN0; ++u) sp[2 * k][u] = load_sp(2 * k, u, lane4);
+                for (int u = 0; u < DVN0; ++u) sp[2 * k][u] = load_sp(2 * k, u);
 #pragma unroll
-                for (int u = 0; u < DVN1; ++u)
-                    if (!(chained(2 * k + 1) && u == DVN1 - 1)) sp[2 * k + 1][u] = load_sp(2 * k + 1, u, lane4);
+                for (int u = 0; u < DVN1; ++u) sp[2 * k + 1][u] = load_sp(2 * k + 1, u);
             }
         };
         int vv[2 * VP];
-        if constexpr (STG) {
-            load_tabs();
-            load_vars_row(vv, lane_bytes());
-        }
         int err0 = 0;
         if constexpr (MC) {
             for (int i = tid; i <= iters; i += T) curve[i] = 0;
@@ -466,54 +281,16 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         } else {
             if constexpr (MSET)
                 for (int i = tid; i < nsw; i += T) syn[i] = 0u;
-            if constexpr (STG) {
-                // every variable is the local one of one check and every thread holds 2 VP of them, so
-                // n = 2 VP Wd: the copy is 2 VP loads per thread, all in flight at once (one HBM round
-                // trip; the loop below takes one per unrolled trip), striding by the launch width, and
-                // covers the row exactly -- nothing is read or staged past variable n - 1.  The rows go
-                // through their descriptor (row_rsrc); group j's offset j Wd is the instruction's scalar
-                // offset (as ld_row's entry), the lane's part one 32-bit byte offset.  wide_io (the
-                // plan: rows 16-byte aligned): VP / 2 groups of four consecutive variables, 16 bytes a
-                // load and an LDS write
-                const __amdgpu_buffer_rsrc_t rl = row_rsrc(a.llr + (size_t)b * n, 4 * n);
-                uint32_t t = (uint32_t)tid;
-                asm volatile("" : "+v"(t));  // as ld_fresh: no index per entry held across the decode
-                if (a.wide_io) {
-                    f32x4 r[VP / 2];
-#pragma unroll
-                    for (int j = 0; j < VP / 2; ++j)
-                        r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rl, 16u * t, 16 * j * Wd, 0));
-#pragma unroll
-                    for (int j = 0; j < VP / 2; ++j) {
-                        f32x4 w;
-                        w.x = to_msg<ALGO>(r[j].x); w.y = to_msg<ALGO>(r[j].y);
-                        w.z = to_msg<ALGO>(r[j].z); w.w = to_msg<ALGO>(r[j].w);
-                        *reinterpret_cast<f32x4 *>(msg + 4u * (t + (uint32_t)(j * Wd))) = w;
-                    }
-                } else {
-                    float r[2 * VP];
-#pragma unroll
-                    for (int i = 0; i < 2 * VP; ++i)
-                        r[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rl, 4u * t, 4 * i * Wd, 0));
-#pragma unroll
-                    for (int i = 0; i < 2 * VP; ++i) msg[t + (uint32_t)(i * Wd)] = to_msg<ALGO>(r[i]);
-                }
-            } else {
-                for (int v = tid; v < n; v += T) msg[v] = to_msg<ALGO>(a.llr[(size_t)b * n + v]);
-            }
+            for (int v = tid; v < n; v += T) msg[v] = to_msg<ALGO>(a.llr[(size_t)b * n + v]);
         }
         __syncthreads();
         if constexpr (MC) {
             const int w = wave_sum(err0);
             if ((tid & (kWave - 1)) == 0) atomicAdd(&curve[0], w);
         }
-        if constexpr (!STG) load_tabs();
+        load_tabs();
         float2 L[VP];  // SPA: E = 2^channel (clamped); min-sum: channel LLR
-        if constexpr (STG) {
-            // every thread of the launch holds all of its 2 VP variables (build_loc_chain_layout)
-#pragma unroll
-            for (int v = 0; v < VP; ++v) L[v] = make_float2(msg[vv[2 * v]], msg[vv[2 * v + 1]]);
-        } else if constexpr (MC) {
+        if constexpr (MC) {
             load_vars(vv);
 #pragma unroll
             for (int v = 0; v < VP; ++v)
@@ -530,15 +307,7 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
         auto init = [&](auto dn_tag, int v) {
             constexpr int DN = decltype(dn_tag)::value;
             float2 w;
-            if constexpr (SPA && STG) {
-                // the wire value clamp(E, 2^-23, 2^23) from the one E = exp2(clamp(L, +-126)): v_exp_f32
-                // is monotone and exact at +-23, so this is exp2(clamp(L, +-23)) to the bit
-                // (scripts/diag/fixed_cost_probe.hip compares the two over every float)
-                L[v] = make_float2(__builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(L[v].x, -126.0f, 126.0f)),
-                                   __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(L[v].y, -126.0f, 126.0f)));
-                w = make_float2(__builtin_amdgcn_fmed3f(L[v].x, 0x1p-23f, 0x1p23f),
-                                __builtin_amdgcn_fmed3f(L[v].y, 0x1p-23f, 0x1p23f));
-            } else if constexpr (SPA) {
+            if constexpr (SPA) {
                 w = make_float2(__builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(L[v].x, -23.0f, 23.0f)),
                                 __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f(L[v].y, -23.0f, 23.0f)));
                 if constexpr (ET)  // the channel decision in the LSB
@@ -557,12 +326,8 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             loc[v] = w;
 #pragma unroll
             for (int u = 0; u < DN; ++u) {
-                if (chained(v) && u == DN - 1) {
-                    chain[v >> 1] = w;
-                } else {
-                    at(pos_lo_x4(sp[v][u])) = w.x;
-                    at(pos_hi_x4(sp[v][u])) = w.y;
-                }
+                at(pos_lo_x4(sp[v][u])) = w.x;
+                at(pos_hi_x4(sp[v][u])) = w.y;
             }
         };
         hbits = 0u;
@@ -610,12 +375,8 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
 #pragma unroll
                 for (int j = DV - 1; j >= 1; --j) {
                     const float2 R = sgn(ratio_wire2(j == DV - 1 ? pre[j] : pre[j] * suf));
-                    if (chained(v) && j == DV - 1) {
-                        chain[v >> 1] = R;
-                    } else {
-                        at(a0[j - 1]) = R.x;
-                        at(a1[j - 1]) = R.y;
-                    }
+                    at(a0[j - 1]) = R.x;
+                    at(a1[j - 1]) = R.y;
                     if (j < DV - 1) suf = suf * cv[j - 1];
                 }
                 if (ep && slab_now) slab[v * T + tid] = loc[v] * suf;  // prod of the incoming c->v ratios
@@ -645,7 +406,7 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
                 for (int v = 0; v < VP; ++v)
 #pragma unroll
                     for (int u = 0; u < DVA; ++u)
-                        if (!(chained(v) && u == DVA - 1)) asm volatile("" : "+v"(sp[v][u]));
+                        asm volatile("" : "+v"(sp[v][u]));
             }
             if constexpr (ALGO == 1) {  // the order masks (ms_sum) are re-derived per iteration, not held
 #pragma unroll
@@ -653,37 +414,8 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             }
             // ---- check phase ----
             if (LDPC_LOC_PRIO) __builtin_amdgcn_s_setprio(0);
-            if constexpr (CL > 0) {
-                // every thread of the launch owns all KP pair slots: no lane test around the phase
-                // (one would cost the loop a register copy per value it rewrites, at the join)
-                const int Tq = Wd;
-                // class 1's rows start behind class 0's two float4 rows of Tq pairs (build_loc_chain_layout:
-                // word 8 Tq; the launcher passes the same as a.loc_cls_w[1])
-                const int W1 = TQ > 0 ? 8 * TQ : a.loc_cls_w[1];
-                // TQ: the last row access, slot KP - 1's float2 row, is the immediate 4 (W1 + 16 Tq + 2 (KP - 2) Tq)
-                // = 120 Tq bytes behind its lane base, within a ds_* instruction's 16-bit offset (64: room for
-                // the kernel's static LDS, 16 bytes, which the compiler folds into the same immediate)
-                static_assert(4 * (8 * TQ + 4 * (KP - 1) * TQ + 2 * (KP - 2) * TQ) + 64 <= 65535,
-                              "the chained rows' offsets are instruction immediates");
 #pragma unroll
-                for (int k = 0; k < KP; ++k) {
-                    // the pair is entry i + off of its class.  TQ: the slot's part is a constant, so every row of
-                    // the phase is a lane base (16 tid or 8 tid bytes, loop-invariant and held in a register
-                    // each) plus an immediate; else the index is recomputed per iteration, as q below
-                    const int off = TQ > 0 && k > 0 ? (k - 1) * TQ : 0;
-                    int i = TQ > 0 ? tid : tid + (k > 0 ? (k - 1) * Tq : 0);
-                    if constexpr (TQ == 0) asm volatile("" : "+v"(i));
-                    if (k == 0)
-                        loc_check_pair<DLO, ALGO>(msg, 0, Tq, i, loc[0], loc[1], a.alpha);
-                    else
-                        loc_check_pair<DLO, ALGO, false, false, CL>(msg, W1, (KP - 1) * Tq, i, loc[2 * k],
-                                                                    loc[2 * k + 1], a.alpha, 0u, &chain[k - 1], off);
-                    if (LDPC_LOC_CGROUP > 0 && k % LDPC_LOC_CGROUP == LDPC_LOC_CGROUP - 1)
-                        __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < (CL > 0 ? 0 : KP); ++k) {
+            for (int k = 0; k < KP; ++k) {
                 int q = tid + k * T;
                 asm volatile("" : "+v"(q));  // recomputed per iteration: no per-pair addresses held live
                 if (q < a.loc_P) {
@@ -864,8 +596,7 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
                 gather(dn_tag, abs_tag, v, sp[v], cv, a0, a1);
             } else {
 #pragma unroll
-                for (int u = 0; u < DN; ++u)
-                    if (!(chained(v) && u == DN - 1)) spv[u] = load_sp(v, u);
+                for (int u = 0; u < DN; ++u) spv[u] = load_sp(v, u);
                 gather(dn_tag, abs_tag, v, spv, cv, a0, a1);
             }
             if constexpr (SPA) {
@@ -911,13 +642,7 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             }
         }
         __syncthreads();  // all gathers done before the staging overwrites messages
-        if constexpr (FIX && CL > 0) {  // every thread of the launch holds all of its variables (see the staging)
-#pragma unroll
-            for (int v = 0; v < VP; ++v) {
-                msg[pid[2 * v]] = pr[v].x;
-                msg[pid[2 * v + 1]] = pr[v].y;
-            }
-        } else if constexpr (FIX) {  // an absent variable (-1) writes the spare word behind variable n - 1
+        if constexpr (FIX) {  // an absent variable (-1) writes the spare word behind variable n - 1
 #pragma unroll
             for (int v = 0; v < VP; ++v) {
                 msg[min((uint32_t)pid[2 * v], (uint32_t)n)] = pr[v].x;
@@ -933,52 +658,9 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
             }
         }
         __syncthreads();
-        if constexpr (FIX && CL > 0) {
-            // n = 2 VP Wd (see the LLR copy): the same strides by the launch width cover the rows exactly,
-            // group j's offset the stores' scalar offset; every LDS read issued before the first store
-            uint32_t t = (uint32_t)tid;
-            asm volatile("" : "+v"(t));  // as ld_fresh: no index per entry held across the decode
-            if (a.wide_io) {
-                f32x4 o[VP / 2];
-#pragma unroll
-                for (int j = 0; j < VP / 2; ++j)
-                    o[j] = *reinterpret_cast<const f32x4 *>(msg + 4u * (t + (uint32_t)(j * Wd)));
-                if (a.post) {
-                    const __amdgpu_buffer_rsrc_t rp = row_rsrc(a.post + (size_t)b * n, 4 * n);
-#pragma unroll
-                    for (int j = 0; j < VP / 2; ++j)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[j] * Domain<ALGO>::out), rp,
-                                                               16u * t, 16 * j * Wd, 0);
-                }
-                if (a.hard) {
-                    const __amdgpu_buffer_rsrc_t rh = row_rsrc(a.hard + (size_t)b * n, n);
-#pragma unroll
-                    for (int j = 0; j < VP / 2; ++j) {
-                        const uint32_t h = (uint32_t)(o[j].x < 0.0f) | (uint32_t)(o[j].y < 0.0f) << 8 |
-                                           (uint32_t)(o[j].z < 0.0f) << 16 | (uint32_t)(o[j].w < 0.0f) << 24;
-                        __builtin_amdgcn_raw_buffer_store_b32(h, rh, 4u * t, 4 * j * Wd, 0);
-                    }
-                }
-            } else {
-                float o[2 * VP];
-#pragma unroll
-                for (int i = 0; i < 2 * VP; ++i) o[i] = msg[t + (uint32_t)(i * Wd)];
-                if (a.post) {
-                    const __amdgpu_buffer_rsrc_t rp = row_rsrc(a.post + (size_t)b * n, 4 * n);
-#pragma unroll
-                    for (int i = 0; i < 2 * VP; ++i)
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[i] * Domain<ALGO>::out), rp, 4u * t,
-                                                              4 * i * Wd, 0);
-                }
-                if (a.hard) {
-                    const __amdgpu_buffer_rsrc_t rh = row_rsrc(a.hard + (size_t)b * n, n);
-#pragma unroll
-                    for (int i = 0; i < 2 * VP; ++i)
-                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(o[i] < 0.0f), rh, t, i * Wd, 0);
-                }
-            }
-        } else if constexpr (FIX) {
-            // n <= 2 VP T (see the LLR copy); rows through their descriptors as there: every LDS read
+        if constexpr (FIX) {
+            // n <= 2 VP T; the rows go through their descriptors (row_rsrc), the lane's part one 32-bit byte
+            // offset: every LDS read
             // issued before the first store, a read past variable n - 1 takes the spare words and its
             // store is dropped.  wide_io: 16 bytes of posteriors and four packed decisions a store
             uint32_t t = (uint32_t)tid;
@@ -1033,6 +715,10 @@ __global__ __launch_bounds__(T, loc_waves_per_simd(T, KP)) void bp_loc_kernel(Bp
     }
 }
 
+// bp_loc_chain.hpp (included by bp_loc_spa.hip only): bp_loc_chain_kernel<KP, T, ...> and its launcher
+template <int KP, int T>
+hipError_t launch_loc_chain(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipStream_t s);
+
 // bp_loc_kernel shapes: (check-degree range, non-local edges per variable, absent edges)
 // x (threads, check pairs per thread)
 template <int DLO, int DHI, int D0, int D1, bool A0, bool A1, int T, int KP, int ALGO, bool ET, bool MC>
@@ -1069,39 +755,9 @@ hipError_t launch_loc_deg(const BpPlan &p, const BpArgs &a, int T, int KP, hipSt
 
 template <int ALGO, bool ET, bool MC>
 hipError_t launch_loc_modes(const BpPlan &p, const ldpc_graph &g, BpArgs a, hipStream_t s) {
-    if (p.chain) {  // the chained layout: its tables, two row classes (pair slot 0 | the chained slots)
-        if constexpr (ALGO == 0 && !ET && !MC) {
-            constexpr int KP = kLocChainKP, T = kLocChainT;
-            // the kernel strides by the launch width and tests no lane: it must be Tq, and the rows 4 KP Tq long
-            if (g.chn_Tq <= 0 || g.chn_Tq > T || g.loc_P != KP * g.chn_Tq || !g.chn_var || !g.chn_pos ||
-                p.width != g.chn_Tq || a.n != 4 * KP * g.chn_Tq)
-                return hipErrorInvalidValue;
-            a.loc_var = g.chn_var;
-            a.loc_pos = g.chn_pos;
-            a.loc_info = g.chn_info;
-            a.loc_P = g.loc_P;
-            a.loc_ncls = 2;
-            a.loc_words = g.chn_words;
-            a.loc_cls_q[0] = 0; a.loc_cls_q[1] = g.chn_Tq; a.loc_cls_q[2] = g.loc_P;
-            a.loc_cls_w[0] = 0; a.loc_cls_w[1] = 8 * g.chn_Tq; a.loc_cls_w[2] = g.chn_words;
-            a.loc_cls_d[0] = a.loc_cls_d[1] = 6;
-            // a plan with a compile-time width (BpPlan::tq): that row's instantiation, which takes Tq, n and the
-            // class table from its template argument -- started on no other width
-            if (p.tq != 0) {
-                if (p.tq != g.chn_Tq) return hipErrorInvalidValue;
-#define LDPC_ROW(TQ)                                                                                           \
-    if (p.tq == TQ)                                                                                            \
-        return launch_lds(bp_loc_kernel<6, 6, 2, 2, KP, T, 0, false, false, false, false, false, kLocChainCL, TQ>, \
-                          dim3(p.grid), dim3(p.width), p.lds, s, a);
-                LDPC_LOC_CHAIN_TQ(LDPC_ROW)
-#undef LDPC_ROW
-                return hipErrorInvalidValue;
-            }
-            auto k = bp_loc_kernel<6, 6, 2, 2, KP, T, 0, false, false, false, false, false, kLocChainCL>;
-            return launch_lds(k, dim3(p.grid), dim3(p.width), p.lds, s, a);
-        } else {
-            return hipErrorInvalidValue;
-        }
+    if (p.chain) {  // the chained layout: a kernel and a launcher of its own, fixed-count sum-product only
+        if constexpr (ALGO == 0 && !ET && !MC) return launch_loc_chain<kLocChainKP, kLocChainT>(p, g, a, s);
+        else return hipErrorInvalidValue;
     }
     a.loc_var = g.loc_var;
     a.loc_pos = g.loc_pos;

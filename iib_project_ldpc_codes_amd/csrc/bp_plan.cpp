@@ -124,11 +124,11 @@ BpPlan bp_plan(const GraphShape &g, int B, int iters, int algo, bool et, bool mc
     size_t slab_per_wg = 0;
     switch (p.path) {
         case BpPath::Loc: {
-            p.name = "bp_loc_kernel";
+            p.name = "bp_loc_kernel";  // the family and its layout: bp_loc_kernel, or bp_loc_chain_kernel for p.chain
             p.threads = g.loc_T;
             const bool mset = et && algo == 1;
             p.lds = loc_lds_bytes(g, iters, mc || mset, mset);
-            // fixed-count sum-product on a graph with a chained layout: its instantiation, its
+            // fixed-count sum-product on a graph with a chained layout: its kernel (bp_loc_chain_kernel), its
             // tables and its (smaller) message LDS; every other mode keeps the plain layout
             p.chain = LDPC_LOC_CHAIN && g.chn_Tq > 0 && algo == 0 && !et && !mc && loc_spare_ok(g.chn_words, g.n);
             if (p.chain) p.lds = pad16(loc_msg_words(g.chn_words, g.n) * 4);

@@ -27,7 +27,7 @@ DropInCache g_dropin;
 // The layout environment, read here and nowhere else: LDPC_NO_LOC_LAYOUT=1 builds no local-edge
 // layout (tests run the other kernels on the same graphs), LDPC_NO_LOC_CHAIN=1 no chained layout
 // beside it (fixed-count sum-product decodes then run on the plain one), LDPC_NO_LOC_TQ=1 keeps the chained
-// layout on the generic instantiation at every width (tests hold the width's own to it), LDPC_LOC_T sets its thread count
+// layout on bp_loc_chain_kernel's generic instantiation at every width (tests hold the width's own to it), LDPC_LOC_T sets its thread count
 // (shape experiments); an explicit loc_T (ldpc_debug_loc_variant) goes over the environment's.
 // LDPC_NO_QC_KERNEL=1 keeps a quasi-cyclic graph's block-row schedule but not its row table
 // (qc_Z = 0): it decodes on the table kernels (tests and A/B runs hold bp_qc_q_kernel to them).

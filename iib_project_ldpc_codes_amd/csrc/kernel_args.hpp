@@ -38,7 +38,7 @@ struct BpArgs {
     // LDS kernel lane layout (ldpc_graph::lane_var / lane_slot)
     const int32_t *lane_var, *lane_slot;
     int lds_slots;  // generic GMEM kernel: message slots [0, lds_slots) kept in LDS
-    int wide_io;    // bp_loc_kernel fixed count: 16-byte row I/O (BpPlan::wide_io); here, in what was padding: no other member moves
+    int wide_io;    // bp_loc_kernel / bp_loc_chain_kernel fixed count: 16-byte row I/O (BpPlan::wide_io); here, in what was padding: no other member moves
     // irregular kernel layout (ldpc_graph::irr_*)
     const int32_t *irr_lane, *irr_cdeg;
     int irr_KC, irr_S, irr_P;
@@ -46,7 +46,7 @@ struct BpArgs {
     const int32_t *loc_var, *loc_pos, *loc_info;
     int loc_P, loc_ncls, loc_words;
     int loc_cls_q[5], loc_cls_d[4], loc_cls_w[5];
-    uint32_t *work;  // bp_loc_kernel early stop (persistent grid): next-codeword counter (zeroed per launch)
+    uint32_t *work;  // bp_loc_kernel early stop (persistent grid): next-codeword counter (zeroed per launch); bp_loc_chain_kernel never reads it
 };
 
 // bp_ens_kernel: codeword b on graph b (rows b of the sampler's lists; cptr / vptr implicit)

@@ -32,7 +32,7 @@
 #define LDPC_LOC_SHAPES(X) X(256, 1) X(256, 2) X(256, 3) X(256, 4) X(1024, 2) X(1024, 3)
 #define LDPC_LOC_REG36_SHAPES(X) X(512, 5)
 #define LDPC_LOC_RSU_SHAPES(X) X(512, 8) X(512, 10)
-// bp_loc_kernel<..., CL, TQ> (bp_loc.hpp): the widths Tq = n / 20 of the chained layout that have an instantiation
+// bp_loc_chain_kernel<KP, T, TQ> (bp_loc_chain.hpp): the widths Tq = n / 20 of the chained layout that have an instantiation
 // of their own, with Tq a compile-time constant.  500: n = 10,000, the benchmark's code.  A width is added for a
 // code that is decoded for long (each row is another 128-VGPR kernel to compile); every other Tq runs the generic one.
 #define LDPC_LOC_CHAIN_TQ(X) X(500)

@@ -148,7 +148,7 @@ inline void loc_shape(const LocLayout &K, GraphShape &g) {
 //   kLocRsu:   <DLO=5, DHI=6, DVN0=1, DVN1=3, ABS0=false, ABS1=true> -- check degrees 5..6, every
 //              slot-0 variable degree 2, slot-1 variables degree 2..4
 //   kLocNone:  no instantiation (the graph runs on bp_lds / bp_irr / bp_generic)
-// Each family has the (T, KP) rows of its shape table (kernel_shapes.hpp), which bp_loc.hpp instantiates.
+// Each family has the (T, KP) rows of its shape table (kernel_shapes.hpp), which bp_loc.hpp instantiates; the chained layout's kernel (bp_loc_chain.hpp) has the one shape kLocChainT x kLocChainKP.
 enum LocVariant { kLocNone = 0, kLocReg36 = 1, kLocRsu = 2 };
 inline int loc_variant(int dlo, int dhi, int DVN, int dvn0, int dvn1, bool abs0, bool abs1, int T, int KP) {
     if (KP <= 0) return kLocNone;
@@ -294,12 +294,12 @@ struct BpPlan {
     // t < Tq own anything; `threads` stays its instantiation's T, the stride of its tables), else `threads`
     int width = 0;
     // bp_plan: the chained call's compile-time width -- `width` when LDPC_LOC_CHAIN_TQ (kernel_shapes.hpp) lists it,
-    // the instantiation bp_loc_kernel<..., CL, tq>; 0: the generic instantiation, and every other call
+    // the instantiation bp_loc_chain_kernel<KP, T, tq>; 0: the generic instantiation, and every other call
     int tq = 0;
     size_t lds = 0;            // dynamic LDS bytes
     int lds_slots = 0;          // bp_generic_kernel / bp_ens_kernel <*,gmem>: message slots [0, lds_slots) kept in LDS
-    bool chain = false;         // bp_loc_kernel: the chained layout's instantiation and tables
-    bool wide_io = false;       // bp_loc_kernel, fixed count: 16-byte row I/O (bp_wide_io; FloodFamily::plan sets it)
+    bool chain = false;         // the chained layout's kernel (bp_loc_chain_kernel) and tables; the plan's name stays the family's
+    bool wide_io = false;       // bp_loc_kernel / bp_loc_chain_kernel, fixed count: 16-byte row I/O (bp_wide_io; FloodFamily::plan sets it)
     bool persistent = false;    // bp_loc_kernel: the grid pulls codewords from a counter in scratch
     size_t slab = 0;            // bytes of per-workgroup slabs at the start of scratch (0: none)
     long counter = -1;          // byte offset of the work counter in scratch (-1: none)

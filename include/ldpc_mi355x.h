@@ -802,7 +802,7 @@ int ldpc_debug_bp_plan_width(const int32_t *check_ptr, const int32_t *check_var,
 /*
  * Host-only: the compile-time width of the same calls; out[i] int64 = Tq when the call is the
  * fixed-count sum-product decode on a chained layout whose Tq has an instantiation of its own
- * (bp_loc_kernel with Tq a template argument: 500, n = 10,000), 0 for every other call and width,
+ * (bp_loc_chain_kernel with Tq a template argument: 500, n = 10,000), 0 for every other call and width,
  * and for every call under LDPC_NO_LOC_TQ=1 (read when the graph's layouts are built).
  */
 int ldpc_debug_bp_plan_tq(const int32_t *check_ptr, const int32_t *check_var, const int32_t *var_ptr,

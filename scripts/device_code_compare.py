@@ -10,9 +10,12 @@ is normalised, cut into kernels, and each kernel instantiation is reduced to an 
 a digest and its resources.  A kernel's own symbol is written <self> in its text, so an instantiation
 whose mangled name alone changed (a template parameter pack added behind the others, empty for it)
 compares equal under its demangled name; --defaulted-arg VALUE does the same for a template argument added
-behind the others with a default.  An instantiation the parent does not have is listed as
-added ("identical": null) and is no difference.  Needs hipcc and git, no GPU.  Exit status 1 when
-anything differs.
+behind the others with a default, --dropped-args N for the last N template arguments taken away (the
+parent's instantiations that had 0 there), and --renamed OLD=NEW for a kernel that moved to another
+template (prefixes of the demangled name).  An instantiation the parent does not have is listed as
+added ("identical": null) and is no difference.  The order of the kernels in each file's assembly -- the
+code object's order -- is compared too ("order_identical", over the kernels both commits have).
+Needs hipcc and git, no GPU.  Exit status 1 when anything differs.
 """
 import argparse
 import hashlib
@@ -110,6 +113,12 @@ def main():
     ap.add_argument("--defaulted-arg", default=None, metavar="VALUE",
                     help="a template argument added behind the others with this default: an instantiation that ends "
                          "', VALUE>' and that the parent lacks is compared with the parent's of the name without it")
+    ap.add_argument("--dropped-args", type=int, default=0, metavar="N",
+                    help="the last N template arguments were taken away: an instantiation that the parent lacks is "
+                         "compared with the parent's of the same leading arguments and N times ', 0' behind them")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW",
+                    help="a parent's kernel whose demangled name starts with OLD is compared under the name with NEW "
+                         "in OLD's place (may be given more than once)")
     ap.add_argument("files", nargs="*")
     a = ap.parse_args()
     files = a.files or default_files()
@@ -120,13 +129,22 @@ def main():
         jobs = [(tree, f) for f in files for tree in (parent, ROOT)]
         with ThreadPoolExecutor(a.jobs) as pool:
             texts = dict(zip(jobs, pool.map(lambda j: assembly(*j), jobs)))
-    rows = []
+    rows, orders = [], []
     for f in files:
         old, new = kernels(texts[(parent, f)]), kernels(texts[(ROOT, f)])
         if a.defaulted_arg is not None:  # the parent's instantiations under the names they have now
             tail = ", %s>(" % a.defaulted_arg
             was = {k.replace(tail, ">(", 1): k for k in new if k not in old and tail in k}
             old = {was.get(k, k): v for k, v in old.items()}
+        for pair in a.renamed:
+            was, now = pair.split("=", 1)
+            old = {now + k[len(was):] if k.startswith(was) else k: v for k, v in old.items()}
+        if a.dropped_args:
+            tail = ", 0" * a.dropped_args + ">("
+            was = {k.replace(">(", tail, 1): k for k in new if k not in old and k.replace(">(", tail, 1) in old}
+            old = {was.get(k, k): v for k, v in old.items()}
+        # dicts keep the assembly's order: the kernels both commits have must come in the same one
+        orders.append([k for k in old if k in new] == [k for k in new if k in old])
         for k in sorted(set(old) | set(new)):
             rows.append({"file": f, "kernel": k, "parent": old.get(k), "new": new.get(k),
                          "identical": old[k] == new.get(k) if k in old else None})
@@ -135,6 +153,7 @@ def main():
     doc = {"what": a.what or "Device code of %s at the parent commit and at this commit, per kernel instantiation."
            % ", ".join(files), "how": HOW, "parent": rev,
            "all_identical": all(r["identical"] for r in rows if r["parent"] is not None),
+           "order_identical": all(orders),
            "instantiations": len(rows), "added": sum(r["parent"] is None for r in rows), "kernels": rows}
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)
@@ -142,8 +161,11 @@ def main():
     differ = [r for r in rows if r["identical"] is False]
     for r in differ:
         print("DIFFERS", r["file"], r["kernel"])
+    for f, same in zip(files, orders):
+        if not same:
+            print("ORDER DIFFERS", f)
     print("%d instantiations in %d files, %d added, %d differ" % (len(rows), len(files), doc["added"], len(differ)))
-    return 1 if differ else 0
+    return 1 if differ or not all(orders) else 0
 
 
 if __name__ == "__main__":

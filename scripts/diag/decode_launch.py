@@ -1,10 +1,10 @@
 """One soft decode launch (or a few) of the bench code ((3,6) n = 10,000, seed 1) for profiling a
-bp_loc_kernel instantiation under rocprofv3: fixed-count / early stop, with / without posteriors,
+bp_loc_kernel / bp_loc_chain_kernel instantiation under rocprofv3: fixed-count / early stop, with / without posteriors,
 sum-product / min-sum; or (--mc-bsc P) one batch of configs[2]'s fused Monte-Carlo (BSC channel,
 normalized min-sum alpha 0.75, early stop: scripts/fer_sweep.py cfg3).  Writes the launch's
 iteration statistics for the issue model.
     python scripts/diag/decode_launch.py --algo spa --et 1 --post 0 [--batch 65536 --iters 50
-        --sigma 0.85 --warmup 0 --reps 1 --out stats.json]
+        --sigma 0.85 --warmup 0 --reps 1 --n 10000 --out stats.json]
     python scripts/diag/decode_launch.py --mc-bsc 0.07 [--batch 65536 ...]"""
 import argparse
 import json
@@ -29,6 +29,8 @@ ap.add_argument("--warmup", type=int, default=0)
 ap.add_argument("--reps", type=int, default=1)
 ap.add_argument("--out", default=None)
 ap.add_argument("--mc-bsc", type=float, default=None)
+ap.add_argument("--rsu", action="store_true", help="the RSU_DL4 ring code (ensembles.py, deg2=path) of length --n: bp_loc_kernel's <5,6,1,3,...> shapes")
+ap.add_argument("--n", type=int, default=10000, help="code length of the soft decode launches (4100: the generic chained kernel)")
 a = ap.parse_args()
 if a.mc_bsc is not None:
     from iib_project_ldpc_codes_amd.montecarlo import MonteCarlo
@@ -53,7 +55,11 @@ if a.mc_bsc is not None:
     if a.out:
         json.dump(out, open(a.out, "w"), indent=1)
     sys.exit(0)
-g = TannerGraph.random_regular(10000, 3, 6, seed=1)
+if a.rsu:
+    from iib_project_ldpc_codes_amd import ensembles
+    g = ensembles.sample_irregular(ensembles.RSU_DL4, a.n, seed=1, deg2="path")
+else:
+    g = TannerGraph.random_regular(a.n, 3, 6, seed=1)
 llr = decoder.channel_dev("awgn", a.sigma, 2026, 0, g.n, a.batch)
 s = torch.cuda.current_stream()
 alpha = 0.75 if a.algo == "minsum" else 1.0
@@ -70,7 +76,7 @@ for r in range(a.warmup + a.reps):
 it = its.cpu().numpy().astype(np.int64)
 stopped = it < a.iters if a.et else np.zeros_like(it, bool)
 out = {"algo": a.algo, "early_stop": bool(a.et), "posteriors": bool(a.post), "batch": a.batch, "iters": a.iters,
-       "sigma": a.sigma, "ms": ts, "kernel": g.kernel_name(early_stop=bool(a.et), hard_only=not a.post),
+       "sigma": a.sigma, "n": g.n, "ms": ts, "kernel": g.kernel_name(early_stop=bool(a.et), hard_only=not a.post),
        "sum_its": int(it.sum()), "mean_its": float(it.mean()), "frac_stopped": float(stopped.mean()),
        # check phases run: stopped frames its + 1 (the last finds every check satisfied), others its;
        # variable phases: stopped frames its, others its - 1 (the last iteration forms posteriors)

@@ -1,10 +1,10 @@
-"""Static instruction counts of one bp_loc_kernel instantiation by section of the compiler's assembly.
+"""Static instruction counts of one bp_loc_chain_kernel / bp_loc_kernel instantiation by section of the compiler's assembly.
 
     python scripts/diag/loc_sections.py <kernels.s> [mangled-symbol-prefix]
 
 <kernels.s>: `hipcc --offload-arch=gfx950 --cuda-device-only -S` of csrc/bp_loc_spa.hip with the Makefile's flags.
-The default symbol is the chained fixed-count instantiation <6,6,2,2,5,512,SPA,CL=4,TQ=500> (the bench code's).  The function is cut at its
-s_barriers, in program order (chained kernel: before the first barrier the codeword claim; then the staging; the
+The default symbol is bp_loc_chain_kernel<5,512,TQ=500> (the bench code's).  The function is cut at its
+s_barriers, in program order (chained kernel: before the first barrier the kernel's entry; then the staging; the
 channel reads; initialisation with, behind it in program order, the rotated loop's variable phase; the check phase;
 the posterior gathers; the scatter; the output tail with the substitution pass behind it), and the decode loop (the
 depth-2 loop of the listing) is counted on its own.  Counts are static: a section that holds two alternative paths
@@ -15,7 +15,7 @@ import json
 import re
 import sys
 
-SYM = "_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb0ELb0ELb0ELi4ELi500EEEvNS_6BpArgsE"
+SYM = "_ZN4ldpc12_GLOBAL__N_119bp_loc_chain_kernelILi5ELi512ELi500EEEvNS_6BpArgsE"
 KEYS = ("scratch_store", "scratch_load", "global_load", "global_store", "buffer_load", "buffer_store", "s_cbranch",
         "s_and_saveexec", "v_lshl_add_u64", "v_ashrrev_i32", "ds_write_b128", "ds_read_b128", "ds_write_b32",
         "ds_read_b32", "v_log", "v_exp", "v_rcp", "v_pk_", "v_readlane", "v_writelane", "s_nop")

@@ -57,18 +57,18 @@ LDS_CYC = {"ds_read_b128": 4, "ds_write_b128": 13, "ds_read_b32": 2, "ds_write_b
 # it undercounts the packed ops' measured cost; both are reported.
 VALU_CYC = {"packed": 5.3, "plain": 4.2, "trans": 8.2}
 KERNELS = {
-    "loc": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb0ELb0ELb0ELi0ELi0EEEvNS",
+    "loc": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb0ELb0ELb0EEEvNS",
             "bp_loc_kernel<6,6,2,2,KP=5,T=512,SPA,fixed-count>", 512, 5),
-    # the chained layout (csrc/loc_layout.cpp): CL = 4 chain links per thread
-    "loc_chain": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb0ELb0ELb0ELi4ELi500EEEvNS",
-                  "bp_loc_kernel<6,6,2,2,KP=5,T=512,SPA,fixed-count,CL=4>", 512, 5),
-    "loc1024": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi3ELi1024ELi0ELb0ELb0ELb0ELb0ELb0ELi0ELi0EEEvNS",
+    # the chained layout (csrc/loc_layout.cpp), KP - 1 = 4 chain links per thread: a kernel of its own
+    "loc_chain": ("_ZN4ldpc12_GLOBAL__N_119bp_loc_chain_kernelILi5ELi512ELi500EEEvNS",
+                  "bp_loc_chain_kernel<KP=5,T=512,TQ=500> (SPA, fixed-count)", 512, 5),
+    "loc1024": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi3ELi1024ELi0ELb0ELb0ELb0ELb0ELb0EEEvNS",
                 "bp_loc_kernel<6,6,2,2,KP=3,T=1024,SPA,fixed-count>", 1024, 3),
-    "loc_et": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb1ELb0ELb0ELi0ELi0EEEvNS",
+    "loc_et": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb1ELb0ELb0EEEvNS",
                "bp_loc_kernel<6,6,2,2,KP=5,T=512,SPA,early-stop>", 512, 5),
-    "loc_ep": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb1ELb0ELb1ELi0ELi0EEEvNS",
+    "loc_ep": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi0ELb0ELb0ELb1ELb0ELb1EEEvNS",
                "bp_loc_kernel<6,6,2,2,KP=5,T=512,SPA,early-stop+posteriors>", 512, 5),
-    "loc_ms": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi1ELb0ELb0ELb0ELb0ELb0ELi0ELi0EEEvNS",
+    "loc_ms": ("_ZN4ldpc12_GLOBAL__N_113bp_loc_kernelILi6ELi6ELi2ELi2ELi5ELi512ELi1ELb0ELb0ELb0ELb0ELb0EEEvNS",
                "bp_loc_kernel<6,6,2,2,KP=5,T=512,min-sum,fixed-count>", 512, 5),
     "lds36": ("_ZN4ldpc12_GLOBAL__N_113bp_lds_kernelILi3ELi6ELi1024ELi10ELi0ELb0ELb0EEEvNS",
               "bp_lds_kernel<3,6,1024,10,SPA,fixed-count>", 1024, None),

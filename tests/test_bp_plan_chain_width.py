@@ -1,7 +1,7 @@
 """Host-only: the launch width of the soft decoders' plans (BpPlan::width, through ldpc_debug_bp_plan_width).
 
 The fixed-count sum-product call on a graph with a chained layout launches that layout's Tq = n / 20 threads
-(bp_loc_kernel<..., CL=4> strides by its launch width and tests no lane): 205, 500 and 510 at n = 4,100 (a
+(bp_loc_chain_kernel strides by its launch width and tests no lane): 205, 500 and 510 at n = 4,100 (a
 part-filled last wave, four waves that are never started), 10,000 (the bench code) and 10,200 (the largest that
 fits).  Every other mode, and every mode under LDPC_NO_LOC_CHAIN=1, launches the plan's `threads`.  The nine
 fields ldpc_debug_bp_plan reports do not move: `threads` stays 512 for the chained call, and each field equals

@@ -1,7 +1,7 @@
 """Host-only: the compile-time width of the soft decoders' plans (BpPlan::tq, through ldpc_debug_bp_plan_tq).
 
 The fixed-count sum-product call on a chained layout whose Tq = n / 20 is listed in LDPC_LOC_CHAIN_TQ
-(kernel_shapes.hpp: 500, n = 10,000) runs bp_loc_kernel<..., CL=4, TQ=500>, whose row offsets are instruction
+(kernel_shapes.hpp: 500, n = 10,000) runs bp_loc_chain_kernel<5, 512, TQ=500>, whose row offsets are instruction
 immediates; the launcher starts that instantiation on a plan that names it and on no other.  Every other width
 (205 at n = 4,100), every other mode, a graph on the plain layout, and every call of a graph built under
 LDPC_NO_LOC_TQ=1 (read with the other layout switches, each time a graph's layouts are built) plan 0: the generic

@@ -1,4 +1,4 @@
-"""bp_loc_kernel on the chained layout (csrc/loc_layout.cpp, build_loc_chain_layout): fixed-count
+"""bp_loc_chain_kernel, the kernel of the chained layout (csrc/bp_loc_chain.hpp; csrc/loc_layout.cpp, build_loc_chain_layout): fixed-count
 sum-product decodes of (3,6) codes at the 512 x 5 shape, n = 4,100 (the smallest: a part-filled
 wave and idle waves) and n = 10,000 (the bench shape), against the oracle and against the same
 decodes on the plain layout (LDPC_NO_LOC_CHAIN=1, a fresh graph handle).  Tolerances are

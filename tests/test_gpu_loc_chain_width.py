@@ -1,4 +1,4 @@
-"""bp_loc_kernel on the chained layout launched Tq threads wide (csrc/bp_loc.hpp: no lane of it tests
+"""bp_loc_chain_kernel launched Tq threads wide (csrc/bp_loc_chain.hpp: no lane of it tests
 tid < Tq, a part-filled last wave is the hardware's EXEC mask, and the LLR copy, the read-back and
 the stores of post / hard stride by the launch width and cover each row exactly).
 

@@ -1,4 +1,4 @@
-"""The staging and the epilogue of bp_loc_kernel's fixed-count decodes (the table loads and the LLR
+"""The staging and the epilogue of bp_loc_kernel's and bp_loc_chain_kernel's fixed-count decodes (the table loads and the LLR
 copy issued together, the wire value from the one exponential; the posterior gathers from the
 loop's positions, each variable id read once, the clamped-exponential test as one ballot with
 its substitution pass behind it, the batched output reads) change no bit of any output.

@@ -1,4 +1,4 @@
-"""The row I/O of bp_loc_kernel's fixed-count decodes: the llr, post and hard rows go through buffer
+"""The row I/O of bp_loc_kernel's and bp_loc_chain_kernel's fixed-count decodes: the llr, post and hard rows go through buffer
 descriptors whose range check stands in for per-element guards, 16 bytes at a time when the plan
 finds the rows aligned (wide_io) and 4 bytes / 1 byte at a time otherwise (or under
 LDPC_NO_WIDE_IO=1).

@@ -1,5 +1,5 @@
-"""bp_loc_kernel<..., CL=4, TQ=500>: the chained fixed-count sum-product decode with its width a compile-time
-constant (csrc/bp_loc.hpp: the check phase's row offsets are instruction immediates, n and the copies' strides fold).
+"""bp_loc_chain_kernel<5, 512, TQ=500>: the chained fixed-count sum-product decode with its width a compile-time
+constant (csrc/bp_loc_chain.hpp: the check phase's row offsets are instruction immediates, n and the copies' strides fold).
 
 The shape is n = 10,000 (Tq = 500), the only one the instantiation accepts: 3 frames at sigma = 0.85, with 1, 2 and 7
 iterations.  post, hard and its of the specialised launch must be np.array_equal to those of the generic
